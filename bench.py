@@ -14,9 +14,14 @@ the interpolation, one persistent kernel); the roofline block names the dominant
 [g R/G, (g+1) R/G)), streamed in batches of 7168 per GPU, per-realization checksums gathered to
 rank 0. Strong scaling (the job is fixed); one step = the whole job.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N; run without a launcher,
     --gpus N > 1 starts that launcher as a child process before anything touches a GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the roofline block comes from HIP events
+inside the timed steps and costs no run of its own). --full adds the measurements that take runs of their own after
+the timed region: the isolated kernels, the exact fused kernel (roofline_exact), the PCIe-inclusive rate, the CPU
+baselines and the C3 / C5 / C4 records. --dump-outputs DIR writes what the last timed step computed as DIR/*.npy.
 
 One process per GPU. RCCL over xGMI (the library's own communicator, fpta_comm_*, on the kernels' HIP runtime;
 fakepta_amd.batch.RcclComm) carries only the barrier, the max-over-ranks time and the checksum gather; the data
@@ -65,6 +70,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=("c2", "c3"))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the measurements that take runs of their own: the isolated "
+                         "kernels, roofline_exact and the PCIe-inclusive rate (--exact-launches), the CPU baselines "
+                         "(--cpu-sample) and the C3 / C5 / C4 records (--sub-configs); without it those three options "
+                         "have no effect")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy (float64; "
+                         "dump_outputs)")
     ap.add_argument("--real", type=int, default=1024, help="c2: realizations per GPU per step")
     ap.add_argument("--c3-real", type=int, default=100000, help="c3: realizations of the whole job")
     # 7168 = 112 blocks of 64 realizations: 100 pulsars x 112 = 11200 k_grid_interp_psr workgroups, 21.9 rounds of
@@ -103,7 +116,10 @@ def parse():
     ap.add_argument("--traffic", default="",
                     help="PMC-derived HBM bytes per launch (profiles/*traffic.json, tools/collect_traffic.py); "
                          "default: the record matching the kernel and shape")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: nothing after the timed region but the outputs and the line
+        args.exact_launches = args.cpu_sample = args.sub_configs = 0
+    return args
 
 
 def refuse_debug_environment():
@@ -338,6 +354,33 @@ def isolated_grid(ctx, capi, sim, seed, R, launches):
         ctx.set_option(capi.OPT_PROFILE, 0)
 
 
+DUMP_BYTES = 48 << 20  # residuals.npy's share of the 64 MB a dump may take (1.6 MB per C2 realization: 31 rows)
+
+
+def dump_outputs(out_dir, ctx, n_toa, sums, block):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as float64 .npy files.
+    checksums.npy: the per-realization (sum, sum of squares) [n, 2] (c2: of the step's block, every rank's; c3: the
+    job's). With block (c2) also residuals.npy, the device-resident [R x n_toa] block of this rank: all of it when it
+    fits DUMP_BYTES, else a fixed seeded sample of its realizations (and of the TOAs when one realization alone is
+    too large), whose indices are residual_rows.npy and residual_cols.npy. The inputs (array seed 0, Philox --seed,
+    the step's first realization) and the sample depend on the arguments only, so two builds compare file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "checksums.npy"), np.ascontiguousarray(sums, dtype=np.float64))
+    if not block:
+        return
+    n_real = ctx.batch_device_out()[2]
+    rng = np.random.default_rng(0)
+    cols = np.arange(n_toa)
+    if 8 * n_toa > DUMP_BYTES:
+        cols = np.sort(rng.choice(n_toa, DUMP_BYTES // 16, replace=False))  # half for the index file
+    n_rows = max(1, min(n_real, DUMP_BYTES // (8 * len(cols))))
+    rows = np.arange(n_real) if n_rows == n_real else np.sort(rng.choice(n_real, n_rows, replace=False))
+    res = np.stack([ctx.batch_download(int(r), 1)[0, :n_toa][cols] for r in rows])
+    np.save(os.path.join(out_dir, "residuals.npy"), res)
+    np.save(os.path.join(out_dir, "residual_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "residual_cols.npy"), cols.astype(np.float64))
+
+
 def launch_ranks(n):
     """--gpus N > 1 without a launcher: run this command under torchrun as N rank processes (a child process;
     nothing here has touched a GPU) and return its exit status."""
@@ -454,6 +497,8 @@ def main():
     synth_n = ctx.kernel_stats(_capi.K_SYNTH)[0]  # launches timed by events (--event-every)
     gi = ctx.batch_grid_info()
     path = gi["last_path"]
+    if args.dump_outputs and rank == 0:  # before anything else synthesizes into the resident block
+        dump_outputs(args.dump_outputs, ctx, info["n_toa"], sums, args.config == "c2")
     # algorithmic bytes of one synthesis launch: 8 B per residual sample written; one launch
     # writes n_toa x R samples (c3: the job's batches averaged, the short last batch included)
     n_launch_real = R if args.config == "c2" else n_job / max(1, -(-shard_bounds(n_job, 0, world)[1] // R))
@@ -565,7 +610,7 @@ def main():
         line = {
             "metric": METRIC, "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": workload, "n_psr": args.npsr, "n_toa_total": info["n_toa"], "K": info["K"],
                        per_key: per_val, "parallelism": "realization-sharded x%d" % world},
             "synth_path": {1: "direct", 2: "mfma", 3: "valu-seeded", 4: "gridded"}.get(path, str(path)),

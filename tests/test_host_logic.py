@@ -242,3 +242,66 @@ def test_bench_refuses_world_size_mismatch():
     res = subprocess.run([sys.executable, "bench.py", "--gpus", "2"], cwd=root, env=env, capture_output=True,
                          text=True, timeout=60)
     assert res.returncode != 0 and "WORLD_SIZE" in res.stderr
+
+
+class _FakeBlock:
+    """Stand-in for a Context holding a resident [R x ld] block (ld > n_toa: padded rows)."""
+
+    def __init__(self, block):
+        self.block = block
+
+    def batch_device_out(self):
+        return 0, self.block.shape[1], self.block.shape[0]
+
+    def batch_download(self, r_begin, r_count):
+        return self.block[r_begin:r_begin + r_count].copy()
+
+
+def test_bench_dump_outputs_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a block within the budget is written whole; a larger one as a fixed seeded sample of
+    its realizations (the same rows on every call), float64, with the padding columns dropped."""
+    import bench
+    rng = np.random.default_rng(5)
+    n_toa = 37
+    block = rng.normal(size=(50, n_toa + 3))
+    sums = np.stack([block[:, :n_toa].sum(1), (block[:, :n_toa] ** 2).sum(1)], 1)
+
+    def dump(name):
+        bench.dump_outputs(str(tmp_path / name), _FakeBlock(block), n_toa, sums, True)
+        return {f: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+
+    whole = dump("whole")
+    assert sorted(whole) == ["checksums.npy", "residual_cols.npy", "residual_rows.npy", "residuals.npy"]
+    assert all(a.dtype == np.float64 for a in whole.values())
+    np.testing.assert_array_equal(whole["residuals.npy"], block[:, :n_toa])
+    np.testing.assert_array_equal(whole["checksums.npy"], sums)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * n_toa * 7)  # room for 7 of the 50 realizations
+    a, b = dump("a"), dump("b")
+    rows = a["residual_rows.npy"].astype(int)
+    assert len(rows) == 7 and len(set(rows)) == 7 and np.all(np.diff(rows) > 0) and rows[-1] < 50
+    np.testing.assert_array_equal(a["residuals.npy"], block[rows, :n_toa])
+    np.testing.assert_array_equal(a["residual_cols.npy"], np.arange(n_toa))
+    for f in a:
+        np.testing.assert_array_equal(a[f], b[f])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 20)  # less than one realization: a sample of the TOAs too
+    c = dump("c")
+    cols = c["residual_cols.npy"].astype(int)
+    assert len(cols) == 10 and np.all(np.diff(cols) > 0) and c["residuals.npy"].shape == (2, 10)
+    np.testing.assert_array_equal(c["residuals.npy"], block[np.ix_(c["residual_rows.npy"].astype(int), cols)])
+    bench.dump_outputs(str(tmp_path / "c3"), None, n_toa, sums, False)  # c3: the job's checksums only
+    assert os.listdir(tmp_path / "c3") == ["checksums.npy"]
+
+
+def test_bench_plain_run_skips_the_full_legs(monkeypatch):
+    """Without --full the options of the legs that run after the timed region have no effect; --full keeps them."""
+    import sys
+
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--exact-launches", "3"])
+    args = bench.parse()
+    assert not args.full and args.dump_outputs == ""
+    assert (args.exact_launches, args.cpu_sample, args.sub_configs) == (0, 0, 0)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--cpu-sample", "2", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "d"
+    assert (args.exact_launches, args.cpu_sample, args.sub_configs) == (5, 2, 1)

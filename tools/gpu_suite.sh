@@ -13,5 +13,5 @@ FAKEPTA_AMD_LIB=build/diag/lib_diag.so timeout -k 10 900 python -u -m pytest tes
 tail -1 ${o}_diag_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > ${o}_smoke.log 2>&1 || { tail -20 ${o}_smoke.log; exit 1; }
 tail -1 ${o}_smoke.log
-timeout -k 10 400 python -u bench.py > ${o}_bench.log 2>&1 || { tail -20 ${o}_bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full > ${o}_bench.log 2>&1 || { tail -20 ${o}_bench.log; exit 1; }
 grep '^{' ${o}_bench.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['ms_per_step'], r['kernel'], r['avg_launch_ms'], r['frac'], r.get('isolated'), r.get('fp64_pipe'), d.get('c5',{}).get('ms_per_step'), d.get('c3',{}).get('ms_per_job'), d.get('c4_per_gpu',{}).get('ms_per_step'))"
