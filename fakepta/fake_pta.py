@@ -14,13 +14,14 @@ Deliberate departures from the reference:
          quantise_ecorr() itself is kept verbatim (D2 preserved there).
   D3     add_system_noise passes PSD kwargs correctly and replaces its own earlier injection.
   D4     add_red_noise(spectrum='custom') injects (the reference silently does nothing).
-  D5     reconstruct_signal(['cgw']) iterates the stored CW entries.
+  D5     add_cgw and reconstruct_signal(['cgw']) evaluate the continuous wave natively (HIP, fakepta_amd/cw.py)
+         instead of importing enterprise_extensions; reconstruction sums every stored CW entry, mapping the stored
+         keys (costheta, phi, ...) to the waveform's parameters (the reference passes them under the wrong names).
   D6     radec_to_thetaphi / thetaphi_to_radec are static methods.
   D7     logging calls are well-formed.
   D9     backend-masked add_time_correlated_noise applies the chromatic factor on the
          masked TOAs (the reference raises a broadcast error for a partial mask).
 """
-import importlib
 import inspect
 import json  # noqa: F401  (reference module namespace parity: pickle/json users)
 import logging
@@ -30,6 +31,7 @@ import numpy as np
 import scipy.constants as sc
 
 from fakepta_amd import _capi
+from fakepta_amd import cw as _cw
 from . import spectrum as _spectrum_module
 
 # PSD registry (fakepta/fake_pta.py:14-22): name -> function, name -> parameter names (minus f)
@@ -42,6 +44,12 @@ _GP_SIGNALS = ("red_noise", "dm_gp", "chrom_gp")
 
 def _df(f):
     return np.diff(np.append(0.0, f))
+
+
+def _cgw_table(entries):
+    """signal_model['cgw'] ({'0': {...}, '1': {...}}, keys = add_cgw's argument names) as source rows [S, 9]."""
+    return np.array([[float(e[k]) for k in _cw.ADD_CGW_KEYS] for e in entries.values()],
+                    dtype=np.float64).reshape(-1, len(_cw.ADD_CGW_KEYS))
 
 
 def _stored_modes(sm):
@@ -404,16 +412,14 @@ class Pulsar:
 
     # ------------------------------------------------------------------ deterministic signals
     def add_cgw(self, costheta, phi, cosinc, log10_mc, log10_fgw, log10_h, phase0, psi, psrterm=False):
-        """Continuous GW from a circular binary via enterprise_extensions (fake_pta.py:422-442).
-        Not part of the accelerated path; needs enterprise_extensions installed."""
-        det = importlib.import_module('enterprise_extensions.deterministic')
+        """Continuous GW from a circular binary (fake_pta.py:422-442), evaluated on the GPU: the signal of
+        enterprise_extensions' cw_delay(evolve=True) without that package (fakepta_amd/cw.py)."""
+        entry = {'costheta': costheta, 'phi': phi, 'cosinc': cosinc, 'log10_mc': log10_mc,
+                 'log10_fgw': log10_fgw, 'log10_h': log10_h, 'phase0': phase0, 'psi': psi, 'psrterm': psrterm}
+        # a refused source (non-finite, coalescing inside the data) raises before anything is recorded
+        _cw.accumulate([self.toas], [self.pos], [_cw.light_seconds(self.pdist)], entry, self.residuals)
         entries = self.signal_model.setdefault('cgw', {})
-        entries[str(len(entries))] = {'costheta': costheta, 'phi': phi, 'cosinc': cosinc, 'log10_mc': log10_mc,
-                                      'log10_fgw': log10_fgw, 'log10_h': log10_h, 'phase0': phase0, 'psi': psi,
-                                      'psrterm': psrterm}
-        self.residuals += det.cw_delay(self.toas, self.pos, self.pdist, cos_gwtheta=costheta, gwphi=phi,
-                                       cos_inc=cosinc, log10_mc=log10_mc, log10_fgw=log10_fgw, evolve=True,
-                                       log10_h=log10_h, phase0=phase0, psi=psi, psrTerm=psrterm)
+        entries[str(len(entries))] = entry
 
     def add_deterministic(self, waveform, **kwargs):
         """Any user waveform(toas=..., **kwargs) (fake_pta.py:444-455)."""
@@ -458,10 +464,9 @@ class Pulsar:
         sig = np.zeros(len(self.toas))
         segs, masks = [], []
         for signal in signals:
-            if signal == 'cgw':
-                det = importlib.import_module('enterprise_extensions.deterministic')
-                for entry in self.signal_model['cgw'].values():
-                    sig += det.cw_delay(self.toas, self.pos, self.pdist, **entry)
+            if signal == 'cgw':  # every stored source in one GPU call
+                _cw.accumulate([self.toas], [self.pos], [_cw.light_seconds(self.pdist)],
+                               _cgw_table(self.signal_model['cgw']), sig)
             if signal in _GP_SIGNALS or 'common' in signal:
                 sm = self.signal_model[signal]
                 f, df, c = _stored_modes(sm)
@@ -492,14 +497,29 @@ class Pulsar:
 def reconstruct_array(psrs, signals=None, freqf=1400):
     """reconstruct_signal (fake_pta.py:526-555, GP branches) for a whole array in ONE GPU launch.
     Returns the list of per-pulsar time series. A pulsar that lacks a requested signal contributes
-    zero for it; pulsars may have different mode counts. (The CW branch is per pulsar: use
-    Pulsar.reconstruct_signal for 'cgw'.)"""
+    zero for it; pulsars may have different mode counts. 'cgw' sums every pulsar's stored continuous
+    waves: one more GPU call for the whole array when all pulsars hold the same sources
+    (add_cgw_array), else one per pulsar that holds any."""
     if signals is None:
         signals = []
         for p in psrs:
             signals += [s for s in p.signal_model if s not in signals]
     offs = np.concatenate([[0], np.cumsum([len(p.toas) for p in psrs])]).astype(np.int64)
     P = len(psrs)
+    cgw = None
+    if 'cgw' in signals:
+        cgw = np.zeros(int(offs[-1]))
+        tabs = [_cgw_table(p.signal_model['cgw']) if 'cgw' in p.signal_model else np.zeros((0, 9)) for p in psrs]
+        if all(t.shape == tabs[0].shape and np.array_equal(t, tabs[0]) for t in tabs):
+            if len(tabs[0]):
+                _cw.accumulate([p.toas for p in psrs], [p.pos for p in psrs],
+                               [_cw.light_seconds(p.pdist) for p in psrs], tabs[0], cgw)
+        else:
+            for i, (p, tab) in enumerate(zip(psrs, tabs)):
+                if len(tab):
+                    part = np.zeros(len(p.toas))
+                    _cw.accumulate([p.toas], [p.pos], [_cw.light_seconds(p.pdist)], tab, part)
+                    cgw[offs[i]:offs[i + 1]] = part
     segs, masks = [], []
     for signal in signals:
         gp = signal in _GP_SIGNALS or 'common' in signal
@@ -535,12 +555,33 @@ def reconstruct_array(psrs, signals=None, freqf=1400):
             backend = signal.split('system_noise_')[1]
             segs.append((f, cc, cs, 0.0, float(freqf)))
             masks.append(np.concatenate([p.backend_flags == backend for p in psrs]))
-    out = np.zeros(int(offs[-1]))
+    out = np.zeros(int(offs[-1])) if cgw is None else cgw
     if segs:
         _capi.get_context().gp_accumulate_array(offs, np.concatenate([p.toas for p in psrs]),
                                                 np.concatenate([p.freqs for p in psrs]), segs, out,
                                                 masks=masks if any(m is not None for m in masks) else None)
     return [out[offs[i]:offs[i + 1]].copy() for i in range(P)]
+
+
+def add_cgw_array(psrs, sources, record=True):
+    """Inject S continuous-wave sources into every pulsar of `psrs` with ONE GPU call (Pulsar.add_cgw per source
+    and pulsar otherwise). sources: [S, 9] rows (cos_gwtheta, gwphi, cos_inc, log10_mc, log10_fgw, log10_h,
+    phase0, psi, psrterm) or a dict of equal-length arrays keyed by add_cgw's argument names. record=True appends
+    one signal_model['cgw'] entry per source to every pulsar, as S add_cgw calls would, so reconstruct_signal /
+    remove_signal work; record=False stores nothing (large populations)."""
+    tab = _cw.source_table(sources)
+    # the device adds into the residuals themselves, as add_cgw does: no zeroed buffer, no host sum
+    res = np.concatenate([np.asarray(p.residuals, dtype=np.float64) for p in psrs])
+    offs = _cw.accumulate([p.toas for p in psrs], [p.pos for p in psrs],
+                          [_cw.light_seconds(p.pdist) for p in psrs], tab, res)
+    for i, p in enumerate(psrs):
+        p.residuals[:] = res[offs[i]:offs[i + 1]]
+        if record:
+            entries = p.signal_model.setdefault('cgw', {})
+            for row in tab:
+                entry = {k: float(v) for k, v in zip(_cw.ADD_CGW_KEYS, row)}
+                entry['psrterm'] = bool(row[-1])
+                entries[str(len(entries))] = entry
 
 
 def make_fake_array(npsrs=25, Tobs=None, ntoas=None, gaps=True, toaerr=None, pdist=None, freqs=[1400],

@@ -38,6 +38,7 @@ _SIGS = [
                                           _dbl, _vp]),
     ("fpta_common_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp,
                                         _vp]),
+    ("fpta_cw_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _dbl, _vp]),
     ("fpta_white_accumulate", _c_int, [_ctx_p, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_gp_covariance", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_noise_wiener", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -106,13 +107,14 @@ OPT_SYNTH_PATH, OPT_MFMA_MIN_REAL, OPT_PROFILE, OPT_ANCHOR, OPT_VALU_VARIANT, OP
 OPT_GRID_WIDTH, OPT_GRID_SIGMA, OPT_GRID_MFMA, OPT_FUSE_CHECKSUMS = 7, 8, 9, 10
 OPT_MIX_MFMA, OPT_OVERLAP, OPT_INTERP_LDS, OPT_GRID_COALESCE, OPT_INTERP_WS, OPT_SIDE_SPLIT = 11, 12, 13, 14, 15, 16
 OPT_DFT_GEN, OPT_GEN_MIX, OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR = 17, 18, 19, 20, 21, 22
-OPT_INTERP_FUSED, OPT_FUSED_WHITE, OPT_FUSED_NEXT_MIX = 23, 24, 25
+OPT_INTERP_FUSED, OPT_FUSED_WHITE, OPT_FUSED_NEXT_MIX, OPT_CW_SPLIT = 23, 24, 25, 26
 OPTIONS = (OPT_SYNTH_PATH, OPT_MFMA_MIN_REAL, OPT_PROFILE, OPT_ANCHOR, OPT_VALU_VARIANT, OPT_FUSE_WHITE,
            OPT_GRID_WIDTH, OPT_GRID_SIGMA, OPT_GRID_MFMA, OPT_FUSE_CHECKSUMS, OPT_MIX_MFMA, OPT_OVERLAP,
            OPT_INTERP_LDS, OPT_GRID_COALESCE, OPT_INTERP_WS, OPT_SIDE_SPLIT, OPT_DFT_GEN, OPT_GEN_MIX,
            OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR, OPT_INTERP_FUSED, OPT_FUSED_WHITE,
-           OPT_FUSED_NEXT_MIX)
-K_GEN, K_MIX, K_SYNTH, K_WHITE, K_DENSE, K_GRID = 0, 1, 2, 3, 4, 5
+           OPT_FUSED_NEXT_MIX, OPT_CW_SPLIT)
+K_GEN, K_MIX, K_SYNTH, K_WHITE, K_DENSE, K_GRID, K_CW = 0, 1, 2, 3, 4, 5, 6
+CW_NPAR = 9  # FPTA_CW_NPAR: cos_gwtheta, gwphi, cos_inc, log10_mc, log10_fgw, log10_h, phase0, psi, psrterm
 
 
 def interp_kernel_name(code):
@@ -293,6 +295,22 @@ class Context:
                                                 float(idx), float(freqf), _ptr(L), _ptr(z), _ptr(residuals),
                                                 _ptr(x)), "fpta_common_accumulate")
         return x
+
+    def cw_accumulate(self, offs, toas, pos, pdist_s, sources, residuals, sign=1.0):
+        """Continuous waves of circular binaries summed into every pulsar (fpta_cw_accumulate). pos [P, 3] unit
+        vectors, pdist_s [P] pulsar distances in light-seconds, sources [S, CW_NPAR]; residuals updated in place."""
+        offs = np.ascontiguousarray(offs, dtype=np.int64)
+        toas, pos, pdist_s = _f64(toas), _f64(pos), _f64(pdist_s)
+        sources = _f64(sources).reshape(-1, CW_NPAR)
+        P, n = len(offs) - 1, int(offs[-1])
+        if not (isinstance(residuals, np.ndarray) and residuals.dtype == np.float64 and residuals.flags.c_contiguous
+                and residuals.flags.writeable and residuals.shape == (n,)):
+            raise ValueError(f"cw_accumulate: residuals must be a writable contiguous float64 array of {n} values")
+        if len(toas) != n or pos.shape != (P, 3) or pdist_s.shape != (P,):
+            raise ValueError(f"cw_accumulate: expected {n} toas, pos [{P}, 3] and pdist_s [{P}]")
+        self._check(_lib.fpta_cw_accumulate(self._h, P, _ptr(offs), _ptr(toas), _ptr(pos), _ptr(pdist_s),
+                                            len(sources), _ptr(sources), float(sign), _ptr(residuals)),
+                    "fpta_cw_accumulate")
 
     def white_accumulate(self, sigma, z, residuals, blocks=None, ecorr_sigma=None, zb=None):
         sigma, z = _f64(sigma), _f64(z)

@@ -237,6 +237,10 @@ struct fpta_ctx {
   // work buffers
   DevBuf coef, zbuf, out, sums, zin, xout, hostz, scratch_out, scratch_z, scratch_zb, scratch_sigma,
       scratch_block_of, scratch_esig, dbg_a, dbg_b;
+  // fpta_cw_accumulate (cw.hip): TOAs, pulsar positions and light-travel times, per-source and per-(pulsar, source)
+  // tables, the 64-TOA wave table, partial sums [n_split][n_toa]
+  DevBuf cw_toas, cw_pos, cw_L, cw_ev, cw_gm, cw_pair, cw_waves, cw_part;
+  int64_t cw_split = 0;  // FPTA_OPT_CW_SPLIT: 0 auto (fpta_cw::split_count), n >= 1 forces n source splits
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
   int32_t out_R = 0;

@@ -98,6 +98,27 @@ int fpta_common_accumulate(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, co
                            double idx, double freqf, const double* L,
                            const double* z, double* residuals, double* x_out);
 
+/* Replaces the enterprise_extensions cw_delay call of fakepta/fake_pta.py:436-441 (Pulsar.add_cgw) and of the 'cgw'
+ * branch of reconstruct_signal, for any number of sources and a whole array in one call (added without a change of
+ * FPTA_VERSION: no existing call changes): the continuous wave of circular binaries with evolving frequency
+ * (cw_delay with evolve=True, tref=0, p_phase=None), source s in src[s][FPTA_CW_NPAR]. With mc = 10^log10_mc Tsun,
+ * w0 = pi 10^log10_fgw, K = 256/5 mc^(5/3) w0^(8/3), omega(x) = w0 (1 - K x)^(-3/8),
+ *   phase(x) = phase0/2 + (w0^(-5/3) - omega(x)^(-5/3)) / (32 mc^(5/3)),   alpha(x) = 10^log10_h / (2 w0^(2/3) omega(x)^(1/3)),
+ *   r(x) = alpha(x) [ sin 2 phase(x) (1 + cos_inc^2) (F+ cos 2 psi - Fx sin 2 psi)
+ *                   + cos 2 phase(x) 2 cos_inc (F+ sin 2 psi + Fx cos 2 psi) ],
+ * F+, Fx, cos mu the antenna pattern of pulsar p (unit vector pos[p]) for the source direction:
+ *   residuals[t in p] += sign * sum_s ( psrterm_s ? r(t - pdist_s[p] (1 - cos mu)) - r(t) : -r(t) )
+ * summed over s in ascending order (in n contiguous pieces when the sources are split, FPTA_OPT_CW_SPLIT). pdist_s:
+ * the pulsar distances in light-seconds. Validated on the host before anything is launched (FPTA_EINVAL, the message
+ * names the source index, residuals untouched): a non-finite parameter, |cos_gwtheta| > 1 or |cos_inc| > 1, or
+ * K max(toas) >= 1 (the binary coalesces inside the data). A source exactly behind a pulsar gives inf / NaN as the
+ * reference's antenna pattern does. n_src == 0 is a successful no-op. */
+#define FPTA_CW_NPAR 9   /* cos_gwtheta, gwphi, cos_inc, log10_mc, log10_fgw, log10_h, phase0, psi, psrterm (0/1) */
+int fpta_cw_accumulate(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const double* toas,
+                       const double* pos /* [n_psr][3] */, const double* pdist_s /* [n_psr] L in seconds */,
+                       int32_t n_src, const double* src /* [n_src][FPTA_CW_NPAR] */,
+                       double sign, double* residuals /* host fp64 [n_toa_total], read and written */);
+
 /* Replaces fakepta/fake_pta.py:201-230 (add_white_noise), with ECORR fixed (defects D1/D2):
  *   residuals[t] += sigma[t] * z[t]  +  sum over blocks b containing t: ecorr_sigma[b] * zb[b]
  * Blocks are CSR: block_offs[n_blocks+1] into block_idx (TOA indices, any order).
@@ -405,6 +426,9 @@ int fpta_comm_gather(fpta_comm* comm, const double* send, int64_t count, double*
                                      with that key then launches no k_gen_mix; after any other call the side streams
                                      wait for the kernel.
                                      0: every block runs k_gen_mix. Results are identical. */
+#define FPTA_OPT_CW_SPLIT 26       /* fpta_cw_accumulate: 0 (default) auto: the source range is split over blocks when
+                                     the TOAs alone leave the device mostly empty (a pure function of n_src and the
+                                     total TOA count); n >= 1 forces n source splits (clamped to n_src). */
 int fpta_set_option(fpta_ctx* ctx, int32_t key, int64_t value);
 /* Current value of option `key` (same keys as fpta_set_option). */
 int fpta_get_option(fpta_ctx* ctx, int32_t key, int64_t* value);
@@ -421,7 +445,8 @@ int fpta_build_flags(void);
 #define FPTA_K_WHITE 3
 #define FPTA_K_DENSE 4 /* dense covariance: basis + Gram, Cholesky, solves, draws */
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
-#define FPTA_K_N 6
+#define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]) */
+#define FPTA_K_N 7
 /* Accumulated launches and HIP-event milliseconds of kernel `which` since the last reset. */
 int fpta_kernel_stats(fpta_ctx* ctx, int32_t which, int64_t* count, double* total_ms);
 int fpta_reset_stats(fpta_ctx* ctx);
