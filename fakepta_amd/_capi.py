@@ -107,12 +107,12 @@ OPT_SYNTH_PATH, OPT_MFMA_MIN_REAL, OPT_PROFILE, OPT_ANCHOR, OPT_VALU_VARIANT, OP
 OPT_GRID_WIDTH, OPT_GRID_SIGMA, OPT_GRID_MFMA, OPT_FUSE_CHECKSUMS = 7, 8, 9, 10
 OPT_MIX_MFMA, OPT_OVERLAP, OPT_INTERP_LDS, OPT_GRID_COALESCE, OPT_INTERP_WS, OPT_SIDE_SPLIT = 11, 12, 13, 14, 15, 16
 OPT_DFT_GEN, OPT_GEN_MIX, OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR = 17, 18, 19, 20, 21, 22
-OPT_INTERP_FUSED, OPT_FUSED_WHITE, OPT_FUSED_NEXT_MIX, OPT_CW_SPLIT = 23, 24, 25, 26
+OPT_INTERP_FUSED, OPT_FUSED_NEXT_MIX, OPT_CW_SPLIT = 23, 25, 26  # key 24 is retired
 OPTIONS = (OPT_SYNTH_PATH, OPT_MFMA_MIN_REAL, OPT_PROFILE, OPT_ANCHOR, OPT_VALU_VARIANT, OPT_FUSE_WHITE,
            OPT_GRID_WIDTH, OPT_GRID_SIGMA, OPT_GRID_MFMA, OPT_FUSE_CHECKSUMS, OPT_MIX_MFMA, OPT_OVERLAP,
            OPT_INTERP_LDS, OPT_GRID_COALESCE, OPT_INTERP_WS, OPT_SIDE_SPLIT, OPT_DFT_GEN, OPT_GEN_MIX,
-           OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR, OPT_INTERP_FUSED, OPT_FUSED_WHITE,
-           OPT_FUSED_NEXT_MIX, OPT_CW_SPLIT)
+           OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR, OPT_INTERP_FUSED, OPT_FUSED_NEXT_MIX,
+           OPT_CW_SPLIT)
 K_GEN, K_MIX, K_SYNTH, K_WHITE, K_DENSE, K_GRID, K_CW = 0, 1, 2, 3, 4, 5, 6
 CW_NPAR = 9  # FPTA_CW_NPAR: cos_gwtheta, gwphi, cos_inc, log10_mc, log10_fgw, log10_h, phase0, psi, psrterm
 
@@ -123,7 +123,7 @@ def interp_kernel_name(code):
     if code <= 0:
         return None
     kind, white, part = (code - 1) >> 2, "true" if (code - 1) & 2 else "false", "true" if (code - 1) & 1 else "false"
-    if kind >= INTERP_KIND_FUSED0:  # launch_grid_fused's / launch_grid_fused_w's instance tables
+    if kind >= INTERP_KIND_FUSED0:  # launch_grid_fused's instance table
         i = kind - INTERP_KIND_FUSED0
         return FUSED_KERNELS[i] if i < len(FUSED_KERNELS) else None
     return {0: f"k_grid_interp_mfma<{white}, {part}, 8>", 1: f"k_grid_interp_ws<{part}>",
@@ -136,8 +136,7 @@ def interp_kernel_name(code):
 # k_grid_fused<NQ, ODD, GEN, HALF> instances in launch_grid_fused's order (capi_host.h kInterpKindFused0 + index)
 INTERP_KIND_FUSED0 = 11
 FUSED_KERNELS = tuple(f"k_grid_fused<{nq}, {odd}, {gen}, {half}>" for nq, half in ((8, "false"), (12, "false"), (8, "true"))
-                      for odd, gen in (("false", "false"), ("false", "true"), ("true", "true"))) + \
-    ("k_grid_fused_w<16, false>", "k_grid_fused_w<16, true>")
+                      for odd, gen in (("false", "false"), ("false", "true"), ("true", "true")))
 BUILD_DEBUG, BUILD_DIAG = 1, 2
 GATHER_AUTO, GATHER_RCCL, GATHER_HOST = 0, 1, 2
 COMM_ID_BYTES = 128

@@ -265,18 +265,8 @@ bool fused_layout(const fpta_ctx* c, const Layout& L) {
          c->interp_ws < 4 && !c->interp_wr && !psr_layout(c, L);
 }
 
-// The gridded plan of L runs white / ECORR blocks (and plain blocks k_grid_fused does not take: three grid signals)
-// on k_grid_fused_w: its 16-realization grids and draw ring fit in LDS (GridPlan::fused_w_ok).
-bool fused_w_layout(const fpta_ctx* c, const Layout& L) {
-  const GridPlan& G = L.grid;
-  return c->fused_white && c->interp_fused && G.built && G.ok && G.fused_w_ok && (c->grid_mfma & 1) && !c->interp_lds &&
-         c->interp_ws < 4 && !c->interp_wr && !psr_layout(c, L);
-}
-
 // The interpolation kernel reads the block's coefficients (pipelined blocks alternate two coefficient buffers)
-bool coef_in_interp(const fpta_ctx* c, const Layout& L) {
-  return psr_layout(c, L) || fused_layout(c, L) || fused_w_layout(c, L);
-}
+bool coef_in_interp(const fpta_ctx* c, const Layout& L) { return psr_layout(c, L) || fused_layout(c, L); }
 
 // FPTA_OPT_FUSED_NEXT_MIX: the common signal whose k_gen_mix a pipelined block of L (R_pad realizations) can take from
 // the previous block's k_grid_fused (FusedMix), or -1: the layout's only common signal, of kMixTiledMinP ..
@@ -589,7 +579,6 @@ struct WhiteCfg {
   const double* esig = nullptr;
   const double* zb = nullptr;
   int64_t nblocks = 0;
-  int64_t zb_ld = 0;  // 0: zb realization-major [R][nblocks]; > 0 epoch-major [nblocks][zb_ld] (k_grid_fused_w only)
   int64_t real0 = 0;
   uint32_t k0 = 0, k1 = 0;
 };
@@ -687,7 +676,6 @@ int run_synth(fpta_ctx* c, Layout& L, int32_t R, int32_t R_pad, double* out, int
       a.w_esig = white->esig;
       a.w_zb = white->zb;
       a.w_nblocks = white->nblocks;
-      a.w_zb_ld = white->zb_ld;
       a.real0 = white->real0;
       a.k0 = white->k0;
       a.k1 = white->k1;
@@ -1005,9 +993,6 @@ int fpta_set_option(fpta_ctx* c, int32_t key, int64_t value) {
       if (value < 0 || value > 3) return fail(c, FPTA_EINVAL, "interp_fused: 0 .. 3");
       c->interp_fused = (int)value;
       return FPTA_OK;
-    case FPTA_OPT_FUSED_WHITE:
-      c->fused_white = value ? 1 : 0;
-      return FPTA_OK;
     case FPTA_OPT_FUSED_NEXT_MIX:
       c->fused_next_mix = value ? 1 : 0;
       return FPTA_OK;
@@ -1083,7 +1068,6 @@ int fpta_get_option(fpta_ctx* c, int32_t key, int64_t* value) {
     case FPTA_OPT_INTERP_PSR: *value = c->interp_psr; return FPTA_OK;
     case FPTA_OPT_INTERP_WR: *value = c->interp_wr; return FPTA_OK;
     case FPTA_OPT_INTERP_FUSED: *value = c->interp_fused; return FPTA_OK;
-    case FPTA_OPT_FUSED_WHITE: *value = c->fused_white; return FPTA_OK;
     case FPTA_OPT_FUSED_NEXT_MIX: *value = c->fused_next_mix; return FPTA_OK;
     case FPTA_OPT_CW_SPLIT: *value = c->cw_split; return FPTA_OK;
   }
@@ -1444,21 +1428,12 @@ int batch_common(fpta_ctx* c, uint64_t seed, int64_t real0, int32_t n_real, cons
   // ECORR epoch normals of this batch as a [R][n_epochs] block, read by every white path. (Making them from their
   // Philox counters inside the gridded epilogue instead was measured 2x slower on C5: the epilogue is VALU-bound,
   // profiles/round4/R4l_c5_storer_ecorr_inline_ab.txt.)
-  // k_grid_fused_w reads them epoch-major (an epoch's realizations contiguous: 16-byte gathers of realization pairs);
-  // the block then runs on it (grid_run checks), no other kernel reads them
   if (do_white && c->has_blocks) {
-    const bool zb_major = path == 4 && c->fuse_white && fused_w_layout(c, L) && !c->fuse_sums;
-    const int64_t ldz = zb_major ? R_pad : 0;
-    HIPCHK(c, c->zb_epochs.ensure(sizeof(double) * (size_t)(zb_major ? R_pad : n_real) * c->n_blocks), "zb alloc");
+    HIPCHK(c, c->zb_epochs.ensure(sizeof(double) * (size_t)n_real * c->n_blocks), "zb alloc");
     wc.zb = c->zb_epochs.as<double>();
-    wc.zb_ld = ldz;
     KTimer kt(c, FPTA_K_WHITE);
-    if (zb_major)
-      HIPCHK(c, launch_epoch_normals_t(c->stream, c->n_blocks, n_real, real0, k0, k1, c->zb_epochs.as<double>(), ldz),
-             "k_epoch_normals_t launch");
-    else
-      HIPCHK(c, launch_epoch_normals(c->stream, c->n_blocks, n_real, real0, k0, k1, c->zb_epochs.as<double>()),
-             "k_epoch_normals launch");
+    HIPCHK(c, launch_epoch_normals(c->stream, c->n_blocks, n_real, real0, k0, k1, c->zb_epochs.as<double>()),
+           "k_epoch_normals launch");
   }
   bool fused = false;
   if (L.segs.empty()) {

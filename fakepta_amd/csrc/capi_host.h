@@ -103,9 +103,6 @@ struct GridPlan {
   // fused_lds the workgroup's LDS bytes
   bool fused_ok = false;
   size_t fused_lds = 0;
-  bool fused_w_ok = false;  // k_grid_fused_w's plan (16-realization grids, <= 3 grid signals); frows serves both
-  size_t fused_w_lds = 0;
-  bool frows_ok = false;
   int32_t fused_fq = 0;  // band steps per (chunk, lane group) in frows
   std::vector<int32_t> fused_lrow0;
   DevBuf frows;
@@ -168,9 +165,6 @@ struct GridPlan {
     wr_ok = false;
     fused_ok = false;
     fused_lds = 0;
-    fused_w_ok = false;
-    fused_w_lds = 0;
-    frows_ok = false;
     fused_lrow0.clear();
     fused_half_ok = false;
     fused_hfq = fused_hvmax = fused_hnq = 0;
@@ -260,7 +254,6 @@ struct fpta_ctx {
   int overlap = 1;
   int interp_ws = 1;      // gridded interpolation on the warp-specialised kernel (FPTA_OPT_INTERP_WS)
   int last_interp = 0;    // interpolation kernel of the last gridded block: 1 + 4 kind + 2 white + part (0: none)
-  int fused_white = 0;  // k_grid_fused_w for white / ECORR and three-grid-signal blocks (FPTA_OPT_FUSED_WHITE)
   double last_fma_interp = 0.0;  // its interpolation MFMA FMAs per realization as run (half-chunk bands: both halves)
   int grid_coalesce = 1;  // gridded path: signals sharing w0 and the chromatic weight share one grid (FPTA_OPT_GRID_COALESCE)
   int part_group = kPartGroup;  // fused partial checksums: consecutive chunks per partial row (FPTA_OPT_PART_GROUP)
@@ -448,7 +441,6 @@ int wait_coef_all(fpta_ctx* c);
 bool grid_gen_fused(const fpta_ctx* c, const Layout& L, size_t g);
 bool psr_layout(const fpta_ctx* c, const Layout& L);
 bool fused_layout(const fpta_ctx* c, const Layout& L);
-bool fused_w_layout(const fpta_ctx* c, const Layout& L);
 int32_t next_mix_seg(const fpta_ctx* c, const Layout& L, int32_t R_pad);
 int batch_common(fpta_ctx* c, uint64_t seed, int64_t real0, int32_t n_real, const double* zin, int32_t zin_nm,
                  double* out, double* coeffs_out, bool white);

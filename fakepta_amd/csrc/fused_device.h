@@ -1,6 +1,6 @@
-// Device helpers shared by the persistent fused kernels (grid_fused.hip: k_grid_fused; grid_fused_w.hip:
-// k_grid_fused_w): per-XCD item queues, the role barrier, the LDS-only wait, a lane-pair DPP exchange, and the
-// FPTA_FUSED_PROF phase counters. Header-only.
+// Device helpers of the persistent fused kernel (grid_fused.hip: k_grid_fused), kept apart from its arithmetic:
+// per-XCD item queues, the role barrier, the LDS-only wait, a lane-pair DPP exchange, and the FPTA_FUSED_PROF phase
+// counters. Header-only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -44,8 +44,9 @@ typedef struct fpta_ctx fpta_ctx;
  * FPTA_OPT_INTERP_WS 0/2/3, DFT_GEN 0, GEN_MIX 0/1/3, ASYNC_SUMS 1 and SIDE_SPLIT 0/1 are refused (FPTA_EINVAL) by
  * the product library (variant builds accept them); FPTA_OPT_INTERP_FUSED takes 0 .. 3; fpta_batch_grid_info_n slot
  * 15 names each k_grid_fused instance (kinds 11 .. 19) instead of kinds 8 / 9. 10200 (round 6): option
- * FPTA_OPT_FUSED_NEXT_MIX; fpta_batch_grid_info_n slots 17 and 18 (FPTA_GRID_INFO_LEN 19). */
-#define FPTA_VERSION 10200
+ * FPTA_OPT_FUSED_NEXT_MIX; fpta_batch_grid_info_n slots 17 and 18 (FPTA_GRID_INFO_LEN 19). 10300: option key 24 is
+ * refused (FPTA_EINVAL); fpta_batch_grid_info_n slot 15 kinds 20 / 21 are gone. */
+#define FPTA_VERSION 10300
 int fpta_version(void);
 int fpta_create(int device, fpta_ctx** out);
 int fpta_destroy(fpta_ctx* ctx);
@@ -242,9 +243,9 @@ int fpta_batch_info(fpta_ctx* ctx, int64_t* info);
  * k_grid_interp_mfma, 1 k_grid_interp_ws, 2 k_grid_interp_ws2, 3 k_grid_interp_lds, 4 k_grid_interp_st, 5
  * k_grid_interp_u, 6 / 7 k_grid_interp_psr with 4 / 8 band steps, 10 k_grid_interp_wr (diagnostic builds only),
  * 11 .. 19 the k_grid_fused<NQ, ODD, GEN, HALF> instances (8 / 12 band steps' operands x no draws / draws / draws
- * from an odd realization, then half-chunk bands x the same three), 20 / 21 k_grid_fused_w (white / ECORR epilogue;
- * even / odd first realization); out[16] (FPTA_VERSION 10100) the interpolation MFMA FMAs per realization of the
- * last gridded block as its kernel ran them (half-chunk bands: both halves' steps; else out[4]); out[17]
+ * from an odd realization, then half-chunk bands x the same three); out[16] (FPTA_VERSION 10100) the interpolation
+ * MFMA FMAs per realization of the last gridded block as its kernel ran them (half-chunk bands: both halves' steps;
+ * else out[4]); out[17]
  * (FPTA_VERSION 10200) 1 when the last block's k_grid_fused also made the next block's common-signal mix
  * (FPTA_OPT_FUSED_NEXT_MIX), out[18] 1 when the last block took its common-signal mix from the previous block's kernel
  * (no k_gen_mix launch).
@@ -410,15 +411,9 @@ int fpta_comm_gather(fpta_comm* comm, const double* send, int64_t count, double*
                                      DFT + interpolation kernels. Whole-chunk bands are bit-identical to the DFT +
                                      interpolation kernels; half-chunk bands group the band rows differently (sums
                                      agree to rounding). A layout k_grid_interp_psr serves keeps it. */
-#define FPTA_OPT_FUSED_WHITE 24   /* (FPTA_VERSION 10100) gridded white / ECORR blocks, and plain blocks of three grid
-                                     signals, whose grids for 16 realizations fit in LDS (C5: 884 rows, 113 KB): 1
-                                     k_grid_fused_w (k_grid_fused's design with 16-realization items, up to 8 DFT
-                                     jobs, the white / ECORR epilogue in the interpolation waves, ECORR epoch normals
-                                     epoch-major); 0 (default) the DFT + interpolation kernels (measured faster on C5:
-                                     1.74 vs 2.05 ms per block). Sums agree to rounding (two summation
-                                     chains per chunk), white / ECORR terms identical. */
+/* key 24 is retired (it was FPTA_OPT_FUSED_WHITE in 10100 .. 10200) and is never to be reused */
 #define FPTA_OPT_FUSED_NEXT_MIX 25 /* (FPTA_VERSION 10200) pipelined gridded blocks on k_grid_fused (FPTA_OPT_OVERLAP 1)
-                                     with one ORF-mixed common signal of 64 .. 128 pulsars drawn by k_gen_mix (C2's
+                                     with one ORF-mixed common signal of 64 .. 256 pulsars drawn by k_gen_mix (C2's
                                      GWB): 1 (default) the kernel's waves with nothing left of their block draw and
                                      mix that signal for the next block of the same seed and size (first realization
                                      real0 + the stride from the block before when that is a whole number of blocks,

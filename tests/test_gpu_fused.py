@@ -245,8 +245,7 @@ def test_fused_pipelined_blocks(ctx, capi, shipped):
 def test_fused_not_taken_outside_its_blocks(ctx, capi, shipped):
     """Blocks k_grid_fused does not serve take the two-kernel path: white / ECORR epilogue, fused partial checksums
     (streamed jobs), three grid signals (a masked backend signal), grids too large for LDS (600 modes: 1,804 grid
-    rows), and FPTA_OPT_INTERP_FUSED 0 (k_grid_fused_w, which could take the first and third, is opt-in:
-    FPTA_OPT_FUSED_WHITE, tests/test_gpu_fused_w.py)."""
+    rows), and FPTA_OPT_INTERP_FUSED 0 (C5-shaped layouts on that path: tests/test_gpu_white_grid.py)."""
     rng = np.random.default_rng(227)
     try:
         offs, toas, nu, segs = _c2_like(ctx, rng, P=12, n=(100, 300))

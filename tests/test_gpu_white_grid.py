@@ -1,11 +1,8 @@
-"""k_grid_fused_w (FPTA_OPT_FUSED_WHITE 1, opt-in: measured slower than the two-kernel path on C5): the
-fused gridded synthesis for white / ECORR blocks and three-grid-signal blocks (C5's shape:
-RN + HD / monopole / dipole common signals in one grid signal, DM and Sv in two more, white noise + 2-TOA ECORR
-epochs), pulsar x 16 realizations per item, against the two-kernel white path it replaces (k_grid_dft_gen +
-k_grid_interp_mfma<true, ..>, FPTA_OPT_INTERP_FUSED 0) and against the oracle.
-
-The kernel sums a chunk's band steps in two chains (even and odd steps) and adds them, so its GP sums differ from the
-two-kernel path's by rounding (checked at W_TOL); the white and ECORR terms are the same operations on the same normals.
+"""Gridded white / ECORR blocks and three-grid-signal blocks on the kernels that ship for them (k_grid_dft_gen +
+k_grid_interp_mfma<true, ..>; plain blocks of such layouts on k_grid_interp_ws), on a ragged C5-like layout: RN + HD /
+monopole / dipole common signals in one grid signal, DM and Sv in two more, white noise + 2-TOA ECORR epochs. Against
+the oracle, pipelined against one-stream, and the kernel choice. (The opt-in fused kernel these layouts once had,
+option key 24, is removed: DESIGN.md §9.)
 
 Reference loops: /root/reference/fakepta/fake_pta.py:201-253 (white / ECORR), 372-387 (per-pulsar GP),
 correlated_noises.py:153-160 (ORF-mixed common signals).
@@ -18,8 +15,6 @@ from tests.conftest import assert_parity, rel_err
 from tests.test_gpu_grid import GRID_TOL, TOL
 
 pytestmark = pytest.mark.gpu
-
-W_TOL = 1e-12  # the same products summed in two chains instead of one (rounding only)
 
 
 @pytest.fixture(scope="module")
@@ -38,15 +33,8 @@ def ctx(capi):
 @pytest.fixture(scope="module")
 def shipped(ctx, capi):
     opts = ctx.options()
-    assert opts[capi.OPT_INTERP_FUSED] == 1 and opts[capi.OPT_FUSED_WHITE] == 0
+    assert opts[capi.OPT_INTERP_FUSED] == 1
     return opts
-
-
-@pytest.fixture(autouse=True)
-def fused_white(ctx, capi, shipped):
-    ctx.set_option(capi.OPT_FUSED_WHITE, 1)
-    yield
-    ctx.set_options(shipped)
 
 
 def _c5_like(ctx, rng, P=17, n=(40, 500), white=True, ecorr=True, sv=True, commons=("hd", "monopole", "dipole")):
@@ -98,8 +86,7 @@ def _c5_like(ctx, rng, P=17, n=(40, 500), white=True, ecorr=True, sv=True, commo
     return offs, toas, nu, segs, sigma, (block_of if ecorr else None), (np.asarray(esig) if ecorr else None)
 
 
-def _run(ctx, capi, fused, seed, real0, R):
-    ctx.set_option(capi.OPT_INTERP_FUSED, fused)
+def _run(ctx, seed, real0, R):
     ctx.batch_synth(seed, 0, R, to_host=False)
     ctx.debug_fill_out(np.nan)
     out = ctx.batch_synth(seed, real0, R)
@@ -107,10 +94,11 @@ def _run(ctx, capi, fused, seed, real0, R):
 
 
 @pytest.mark.parametrize("case", ["white_ecorr", "white", "ecorr", "plain", "two_grid_white"])
-def test_fused_w_matches_two_kernel_path_and_oracle(ctx, capi, shipped, case):
-    """k_grid_fused_w against the two-kernel path (INTERP_FUSED 0) at W_TOL and the oracle at the gridded tolerance:
-    realization counts off the 16-realization items (R_pad padding), odd first realizations (the ODD draws and the
-    white stream's misaligned quads), every sample written (NaN-poisoned block), the kernel that ran named."""
+def test_c5_like_layouts_match_oracle(ctx, capi, shipped, case):
+    """The shipped options (+ FPTA_OPT_SYNTH_PATH 4) against the oracle at the gridded tolerance: realization counts off
+    the realization tiles (R_pad padding), odd first realizations (the white stream's misaligned quads), every sample
+    written (NaN-poisoned block), no k_grid_fused instance. R = 333 and 100: the whole block; R = 16 and 1024: the
+    first, a middle and the last realization, each against the oracle's one-realization range."""
     rng = np.random.default_rng(401 + len(case))
     kw = dict(white=case in ("white_ecorr", "white", "two_grid_white"), ecorr=case in ("white_ecorr", "ecorr"),
               sv=case != "two_grid_white")
@@ -118,26 +106,28 @@ def test_fused_w_matches_two_kernel_path_and_oracle(ctx, capi, shipped, case):
     try:
         ctx.set_option(capi.OPT_SYNTH_PATH, 4)
         for R, real0 in ((333, 5), (16, 0), (100, 77), (1024, 3)):
-            ref, k0 = _run(ctx, capi, 0, 13, real0, R)
-            got, k1 = _run(ctx, capi, 1, 13, real0, R)
-            assert k1 == f"k_grid_fused_w<16, {'true' if real0 & 1 else 'false'}>", k1
-            assert not k0.startswith("k_grid_fused"), k0
+            got, k = _run(ctx, 13, real0, R)
             assert np.all(np.isfinite(got))
-            assert rel_err(got, ref) <= W_TOL, (R, real0, rel_err(got, ref))
+            assert not k.startswith("k_grid_fused"), k
             if R in (333, 100):
                 want = O.batch_synth(offs, toas, nu, segs, 13, real0, R, sigma=sigma, block_of=block_of,
                                      ecorr_sigma=esig)
-                assert rel_err(got, want) <= GRID_TOL
-                assert_parity(got, want, TOL)
+            else:
+                rows = [0, R // 2 - 1, R - 1]
+                want = np.concatenate([O.batch_synth(offs, toas, nu, segs, 13, real0 + r, 1, sigma=sigma,
+                                                     block_of=block_of, ecorr_sigma=esig) for r in rows])
+                got = got[rows]
+            assert rel_err(got, want) <= GRID_TOL, (R, real0, rel_err(got, want))
+            assert_parity(got, want, TOL)
     finally:
         ctx.batch_set_white()
         ctx.batch_clear()
         ctx.set_options(shipped)
 
 
-def test_fused_w_pipelined_blocks_and_determinism(ctx, capi, shipped):
+def test_pipelined_blocks_and_determinism(ctx, capi, shipped):
     """Pipelined blocks (FPTA_OPT_OVERLAP 1: the next block's common draws into the other coefficient buffer on the
-    side stream while this block's kernel reads its own) equal one-stream blocks bit for bit, run to run, with their
+    side stream while this block's kernels read their own) equal one-stream blocks bit for bit, run to run, with their
     checksums; batch-split invariance (a realization's samples do not depend on the block it is drawn in)."""
     rng = np.random.default_rng(433)
     _c5_like(ctx, rng, P=20, n=(200, 700))
@@ -149,7 +139,7 @@ def test_fused_w_pipelined_blocks_and_determinism(ctx, capi, shipped):
             for b in range(3):
                 ctx.batch_synth(29, 256 * b, 256, to_host=False)
             res[ov, "last"] = ctx.batch_synth(29, 256 * 3, 256)
-            assert ctx.batch_grid_info()["interp_kernel"].startswith("k_grid_fused_w")
+            assert not ctx.batch_grid_info()["interp_kernel"].startswith("k_grid_fused")
             res[ov, "each"] = [(ctx.batch_synth(29, 300 * b + 1, 300), ctx.batch_checksums()) for b in range(3)]
         np.testing.assert_array_equal(res[0, "last"], res[1, "last"])
         for (x, xs), (y, ys) in zip(res[0, "each"], res[1, "each"]):
@@ -164,45 +154,44 @@ def test_fused_w_pipelined_blocks_and_determinism(ctx, capi, shipped):
         ctx.set_options(shipped)
 
 
-def test_fused_w_not_taken_outside_its_blocks(ctx, capi, shipped):
-    """Blocks k_grid_fused_w does not serve take the other kernels: fused partial checksums (streamed jobs), grids
-    too large for LDS at 16 realizations (three signals of 600 modes), FPTA_OPT_INTERP_FUSED 0; and a plain block of
-    a two-grid-signal layout stays on k_grid_fused."""
+def test_kernel_choice_and_retired_key(ctx, capi, shipped):
+    """A plain block of a two-grid-signal layout runs on k_grid_fused; the same layout with white noise takes the DFT +
+    interpolation kernels. Option key 24 (the removed kernel's) is refused by set_option and get_option."""
     rng = np.random.default_rng(439)
     try:
-        offs, toas, nu, segs, sigma, block_of, esig = _c5_like(ctx, rng, P=8, n=(100, 300))
-        ctx.set_option(capi.OPT_SYNTH_PATH, 4)
-        ctx.batch_synth(3, 0, 256, to_host=False)
-        assert ctx.batch_grid_info()["interp_kernel"].startswith("k_grid_fused_w")
-        ctx.set_option(capi.OPT_FUSE_CHECKSUMS, 1)
-        ctx.batch_synth(3, 0, 256, to_host=False)
-        assert not ctx.batch_grid_info()["interp_kernel"].startswith("k_grid_fused")
-        ctx.set_option(capi.OPT_FUSE_CHECKSUMS, 0)
-        ctx.set_option(capi.OPT_INTERP_FUSED, 0)
-        ctx.batch_synth(3, 0, 256, to_host=False)
-        assert not ctx.batch_grid_info()["interp_kernel"].startswith("k_grid_fused")
-        ctx.set_options(shipped)
-        ctx.set_option(capi.OPT_FUSED_WHITE, 1)
-        ctx.batch_set_white()
-        ctx.batch_clear()
-        _c5_like(ctx, rng, P=6, n=(100, 300), white=False, ecorr=False, sv=False)
+        offs = _c5_like(ctx, rng, P=6, n=(100, 300), white=False, ecorr=False, sv=False)[0]
         ctx.set_option(capi.OPT_SYNTH_PATH, 4)
         ctx.batch_synth(3, 0, 256, to_host=False)
         k = ctx.batch_grid_info()["interp_kernel"]
         assert k.startswith("k_grid_fused<"), k
+        ctx.batch_set_white(rng.uniform(0.5e-7, 2e-7, offs[-1]), [], [])
+        ctx.batch_synth(3, 0, 256, to_host=False)
+        k = ctx.batch_grid_info()["interp_kernel"]
+        assert not k.startswith("k_grid_fused"), k
+        with pytest.raises(capi.FptaError):
+            ctx.set_option(24, 1)
+        with pytest.raises(capi.FptaError):
+            ctx.get_option(24)
+    finally:
+        ctx.batch_set_white()
         ctx.batch_clear()
-        # three 600-mode signals: 3 x 1,804 grid rows do not fit in LDS even at 16 realizations
-        P = 3
-        offs = np.array([0, 200, 400, 600], dtype=np.int64)
-        t = np.sort(rng.uniform(4.4e9, 4.4e9 + 3.15e8, 600))
-        ctx.batch_set_toas(offs, t, rng.choice([800.0, 1400.0, 2500.0], size=600))
-        T = t.max() - t.min()
-        for idx in (0.0, 2.0, 4.0):
-            f = np.tile(np.arange(1, 601) / T, (P, 1))
-            ctx.batch_add_signal(0, f, np.sqrt(O.powerlaw(f, -14.0, 3.0) / T), idx=idx)
-        ctx.batch_set_white(np.full(600, 1e-7), [], [])
-        ctx.batch_synth(3, 0, 64, to_host=False)
-        assert not ctx.batch_grid_info()["interp_kernel"].startswith("k_grid_fused")
+        ctx.set_options(shipped)
+
+
+def test_coeffs_after_pipelined_ecorr_blocks(ctx, capi, shipped):
+    """A coefficient download after pipelined ECORR blocks (FPTA_OPT_OVERLAP 1) succeeds and changes no sample: the
+    block reads its epoch normals realization-major whichever way its coefficients are drawn. (With the removed
+    kernel's option on, this call failed with FPTA_ESTATE.)"""
+    rng = np.random.default_rng(443)
+    _c5_like(ctx, rng, P=8, n=(100, 300))
+    try:
+        ctx.set_option(capi.OPT_SYNTH_PATH, 4)
+        ctx.set_option(capi.OPT_OVERLAP, 1)
+        for b in range(2):
+            ctx.batch_synth(7, 256 * b, 256, to_host=False)
+        out, co = ctx.batch_synth(7, 512, 64, coeffs=True)
+        assert np.all(np.isfinite(out)) and np.all(np.isfinite(co))
+        np.testing.assert_array_equal(out, ctx.batch_synth(7, 512, 64))
     finally:
         ctx.batch_set_white()
         ctx.batch_clear()
