@@ -191,12 +191,52 @@ def add_common_correlated_noise(psrs, orf='hd', spectrum='powerlaw', name='gw', 
         np.random.standard_normal(P)
         raise IndexError(f'index {2 * len(f_psd)} is out of bounds for axis 0 with size {2 * len(f_psd)}')
 
-def add_roemer_delay(psrs, planet, d_mass=0., d_Om=0., d_omega=0., d_inc=0., d_a=0., d_e=0., d_l0=0.):
-    """Ephemeris-error Roemer delay (correlated_noises.py:163-172). Deterministic, not part of the
-    accelerated path: needs a Pulsar built with an `ephem` object exposing roemer_delay()."""
+def _native_ephem(psrs):
+    """The native Ephemeris every pulsar shares, or None (no pulsars, different objects, or a user's own class)."""
+    from .ephemeris import Ephemeris
+    first = psrs[0].ephem if len(psrs) else None
+    if isinstance(first, Ephemeris) and all(p.ephem is first for p in psrs):
+        return first
+    return None
+
+
+def add_roemer_delay_array(psrs, perturbations):
+    """Sum of several ephemeris-error Roemer delays added to every pulsar. perturbations: a list of
+    (planet, deviations), deviations a dict with any of d_mass, d_Om, d_omega, d_inc, d_a, d_e, d_l0. When every
+    pulsar carries the same native Ephemeris the whole array and all perturbations run in one GPU call
+    (fpta_roemer_accumulate); otherwise each pulsar's own `ephem.roemer_delay` is called per perturbation."""
     for p in psrs:
         if not hasattr(p, 'ephem'):
             print('"ephem" not found in pulsar', p.name)
             return
+    perturbations = [(planet, dict(dev)) for planet, dev in perturbations]
+    ephem = _native_ephem(psrs)
+    if ephem is None:
+        for p in psrs:
+            for planet, dev in perturbations:
+                p.residuals += p.ephem.roemer_delay(p.toas, p.pos, planet, **dev)
+        return
+    if not perturbations:
+        return
+    from fakepta_amd import ephem as _ephem
+    rows = [ephem.roemer_row(planet, **dev) for planet, dev in perturbations]
+    res = np.concatenate([p.residuals for p in psrs])
+    offs = _ephem.accumulate([p.toas for p in psrs], [p.pos for p in psrs], rows, res)
+    for n, p in enumerate(psrs):
+        p.residuals[:] = res[offs[n]:offs[n + 1]]
+
+
+def add_roemer_delay(psrs, planet, d_mass=0., d_Om=0., d_omega=0., d_inc=0., d_a=0., d_e=0., d_l0=0.):
+    """Ephemeris-error Roemer delay (correlated_noises.py:163-172). With the native fakepta.ephemeris.Ephemeris shared
+    by every pulsar the whole array runs in one GPU call; with any other `ephem` object its own roemer_delay() is
+    called per pulsar, as in the reference."""
+    for p in psrs:
+        if not hasattr(p, 'ephem'):
+            print('"ephem" not found in pulsar', p.name)
+            return
+    if _native_ephem(psrs) is not None:
+        add_roemer_delay_array(psrs, [(planet, dict(d_mass=d_mass, d_Om=d_Om, d_omega=d_omega, d_inc=d_inc, d_a=d_a,
+                                                    d_e=d_e, d_l0=d_l0))])
+        return
     for p in psrs:
         p.residuals += p.ephem.roemer_delay(p.toas, p.pos, planet, d_mass, d_Om, d_omega, d_inc, d_a, d_e, d_l0)

@@ -39,6 +39,9 @@ _SIGS = [
     ("fpta_common_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp,
                                         _vp]),
     ("fpta_cw_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _dbl, _vp]),
+    ("fpta_ephem_kepler", _c_int, [_ctx_p, _i64, _vp, _vp, _vp]),
+    ("fpta_ephem_orbits", _c_int, [_ctx_p, _i64, _vp, _i32, _vp, _vp, _vp]),
+    ("fpta_roemer_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _dbl, _i32, _vp]),
     ("fpta_white_accumulate", _c_int, [_ctx_p, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_gp_covariance", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_noise_wiener", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -113,8 +116,12 @@ OPTIONS = (OPT_SYNTH_PATH, OPT_MFMA_MIN_REAL, OPT_PROFILE, OPT_ANCHOR, OPT_VALU_
            OPT_INTERP_LDS, OPT_GRID_COALESCE, OPT_INTERP_WS, OPT_SIDE_SPLIT, OPT_DFT_GEN, OPT_GEN_MIX,
            OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR, OPT_INTERP_FUSED, OPT_FUSED_NEXT_MIX,
            OPT_CW_SPLIT)
-K_GEN, K_MIX, K_SYNTH, K_WHITE, K_DENSE, K_GRID, K_CW = 0, 1, 2, 3, 4, 5, 6
+K_GEN, K_MIX, K_SYNTH, K_WHITE, K_DENSE, K_GRID, K_CW, K_EPHEM = 0, 1, 2, 3, 4, 5, 6, 7
 CW_NPAR = 9  # FPTA_CW_NPAR: cos_gwtheta, gwphi, cos_inc, log10_mc, log10_fgw, log10_h, phase0, psi, psrterm
+EPHEM_NBODY = 14  # FPTA_EPHEM_NBODY: mass, T, then (value, rate per century) of inc, Om, omega, a, e, l0
+ROEMER_NPAR = 22  # FPTA_ROEMER_NPAR: a body, d_mass, d_Om, d_omega, d_inc, d_a, d_e, d_l0, 1 / mass_ss
+EPHEM_E_MAX = 0.95  # FPTA_EPHEM_E_MAX
+EPHEM_MSUN = 1.327124400e20 / 6.6743e-11  # FPTA_EPHEM_MSUN
 
 
 def interp_kernel_name(code):
@@ -310,6 +317,46 @@ class Context:
         self._check(_lib.fpta_cw_accumulate(self._h, P, _ptr(offs), _ptr(toas), _ptr(pos), _ptr(pdist_s),
                                             len(sources), _ptr(sources), float(sign), _ptr(residuals)),
                     "fpta_cw_accumulate")
+
+    def ephem_kepler(self, M, e):
+        """E with E - e sin E = M, elementwise (fpta_ephem_kepler); M and e broadcast against each other."""
+        M, e = np.broadcast_arrays(np.asarray(M, dtype=np.float64), np.asarray(e, dtype=np.float64))
+        shape = M.shape
+        M, e = _f64(M).ravel(), _f64(e).ravel()
+        out = np.empty(M.size)
+        self._check(_lib.fpta_ephem_kepler(self._h, M.size, _ptr(M), _ptr(e), _ptr(out)), "fpta_ephem_kepler")
+        return out.reshape(shape)
+
+    def ephem_orbits(self, toas, bodies, planets=True, sun=False):
+        """(planetssb [n, B, 6] or None, sunssb [n, 3] or None) of the body table [B, EPHEM_NBODY] at the TOAs
+        (fpta_ephem_orbits)."""
+        toas = _f64(toas).ravel()
+        bodies = _f64(bodies).reshape(-1, EPHEM_NBODY)
+        if not (planets or sun):
+            raise ValueError("ephem_orbits: ask for planets, sun or both")
+        # zero-filled: with no TOAs or no bodies the call writes nothing
+        pssb = np.zeros((len(toas), len(bodies), 6)) if planets else None
+        sssb = np.zeros((len(toas), 3)) if sun else None
+        self._check(_lib.fpta_ephem_orbits(self._h, len(toas), _ptr(toas), len(bodies), _ptr(bodies), _ptr(pssb),
+                                           _ptr(sssb)), "fpta_ephem_orbits")
+        return pssb, sssb
+
+    def roemer_accumulate(self, offs, toas, pos, rows, out, sign=1.0, separate=False):
+        """Roemer delays of the rows [R, ROEMER_NPAR] for every pulsar (fpta_roemer_accumulate). pos [P, 3]; out
+        [n] updated in place (out += sign * sum of the rows' delays), or with separate [R, n] written."""
+        offs = np.ascontiguousarray(offs, dtype=np.int64)
+        toas, pos = _f64(toas), _f64(pos)
+        rows = _f64(rows).reshape(-1, ROEMER_NPAR)
+        P, n = len(offs) - 1, int(offs[-1])
+        shape = (len(rows), n) if separate else (n,)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous
+                and out.flags.writeable and out.shape == shape):
+            raise ValueError(f"roemer_accumulate: out must be a writable contiguous float64 array of shape {shape}")
+        if len(toas) != n or pos.shape != (P, 3):
+            raise ValueError(f"roemer_accumulate: expected {n} toas and pos [{P}, 3]")
+        self._check(_lib.fpta_roemer_accumulate(self._h, P, _ptr(offs), _ptr(toas), _ptr(pos), len(rows), _ptr(rows),
+                                                float(sign), int(bool(separate)), _ptr(out)),
+                    "fpta_roemer_accumulate")
 
     def white_accumulate(self, sigma, z, residuals, blocks=None, ecorr_sigma=None, zb=None):
         sigma, z = _f64(sigma), _f64(z)

@@ -235,6 +235,9 @@ struct fpta_ctx {
   // tables, the 64-TOA wave table, partial sums [n_split][n_toa]
   DevBuf cw_toas, cw_pos, cw_L, cw_ev, cw_gm, cw_pair, cw_waves, cw_part;
   int64_t cw_split = 0;  // FPTA_OPT_CW_SPLIT: 0 auto (fpta_cw::split_count), n >= 1 forces n source splits
+  // fpta_ephem_* / fpta_roemer_accumulate (ephem.hip): TOAs (or M), the body / row table (or e), pulsar positions,
+  // the 64-TOA wave table, the output (planetssb, delays, residuals or E) and sunssb
+  DevBuf eph_toas, eph_tab, eph_pos, eph_waves, eph_out, eph_sun;
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
   int32_t out_R = 0;

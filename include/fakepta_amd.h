@@ -120,6 +120,54 @@ int fpta_cw_accumulate(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const 
                        int32_t n_src, const double* src /* [n_src][FPTA_CW_NPAR] */,
                        double sign, double* residuals /* host fp64 [n_toa_total], read and written */);
 
+/* Replaces fakepta/ephemeris.py (Ephemeris.solve_kepler_equation, compute_orbit, get_planet_ssb, get_sunssb,
+ * roemer_delay: one scipy newton call per (TOA, body) and a Python rotation per sample) for any number of bodies and a
+ * whole array in one call (added without a change of FPTA_VERSION: no existing call changes). This text is the
+ * specification.
+ * A body is FPTA_EPHEM_NBODY doubles: mass, T [days], then (value, rate per Julian century) of inc, Om, omega [deg],
+ * a [AU], e, l0 [deg]. a = None of the reference is the pair (0, 0): it stands for the Kepler-law value
+ * (GMsun (86400 T)^2 / (4 pi^2))^(1/3) / AU with rate 0 (GMsun = 1.327124400e20), resolved on the host.
+ * For a TOA in MJD seconds, t = (toa / 86400 - 51544.5) / 36525 (the reference adds 2400000.5 days first, which costs
+ * ~1e-14 century; 51544.5 is exact). Every element is value + rate t. With a_s = a AU / c [s],
+ *   M = mod((l0 - omega) pi / 180, 2 pi),   E - e sin E = M,
+ *   x = a_s cos(E - e),   y = a_s sqrt(1 - e^2) sin E     (the reference's x, not a_s (cos E - e): kept)
+ *   orbit = R_x(eps) R_z(Om) R_x(inc) R_z(omega - Om) (x, y, 0)^T,   eps = 23.43928 deg, angles in radians,
+ * i.e. with O = Om, w = omega - Om, i = inc:
+ *   X = (cos O cos w - sin O cos i sin w) x + (-cos O sin w - sin O cos i cos w) y
+ *   Y = (sin O cos w + cos O cos i sin w) x + (-sin O sin w + cos O cos i cos w) y
+ *   Z = sin i sin w x + sin i cos w y,       orbit = (X, cos eps Y - sin eps Z, sin eps Y + cos eps Z)  [light-seconds].
+ * Kepler's equation is solved by Newton's method for 0 <= e <= FPTA_EPHEM_E_MAX.
+ * Validated on the host before anything is uploaded or launched (FPTA_EINVAL, the message names the TOA, body or row
+ * index, the outputs untouched): a non-finite value; e(t) outside [0, FPTA_EPHEM_E_MAX] or a(t) <= 0 at either end of
+ * the TOA span (the elements are linear, so the ends suffice); a = None without T > 0; 1 / mass_ss <= 0. */
+#define FPTA_EPHEM_NBODY 14
+#define FPTA_EPHEM_E_MAX 0.95
+#define FPTA_EPHEM_MSUN (1.327124400e20 / 6.6743e-11) /* kg: GMsun / G */
+/* E_out[i] with E - e[i] sin E = M[i]; whole turns of M are taken off before the solve and put back after it. */
+int fpta_ephem_kepler(fpta_ctx* ctx, int64_t n, const double* M, const double* e, double* E_out);
+/* planetssb_out (or NULL): [n_toa][n_body][6], columns 0 .. 2 the orbit of each body in table order, columns 3 .. 5
+ * (the velocities, which the reference leaves uninitialised) 0. sunssb_out (or NULL): [n_toa][3] =
+ * -sum_b mass_b / FPTA_EPHEM_MSUN orbit_b, summed in table order. At least one output. */
+int fpta_ephem_orbits(fpta_ctx* ctx, int64_t n_toa, const double* toas, int32_t n_body,
+                      const double* bodies /* [n_body][FPTA_EPHEM_NBODY] */, double* planetssb_out,
+                      double* sunssb_out);
+/* Roemer delay of ephemeris errors (Ephemeris.roemer_delay, correlated_noises.add_roemer_delay). Row r is a body, then
+ * d_mass, d_Om, d_omega, d_inc, d_a, d_e, d_l0, then 1 / mass_ss (mass_ss in the unit of mass and d_mass):
+ *   delay_r(t in p) = [ (mass + d_mass) orbit'(t) - mass orbit(t) ] / mass_ss . pos[p]
+ * orbit from the row's elements as given, orbit' from the elements with the six deviations added to their values (not
+ * to the rates; d_a is added to the resolved a). The reference adds the deviations to its stored table and evaluates
+ * both orbits from it, so it returns 0 for element deviations and drifts from call to call; this is the expression it
+ * states. When all six element deviations are exactly 0 the orbit is evaluated once.
+ *   separate == 0: out[t] += sign * sum_r delay_r(t)   (out: [n_toa_total], read and written; rows summed in
+ *                  ascending order in one register per TOA)
+ *   separate != 0: out[r][t] = sign * delay_r(t)       (out: [n_row][n_toa_total], written)
+ * A pulsar may have no TOAs. n_row == 0 is a successful no-op. */
+#define FPTA_ROEMER_NPAR 22
+int fpta_roemer_accumulate(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const double* toas,
+                           const double* pos /* [n_psr][3] */, int32_t n_row,
+                           const double* rows /* [n_row][FPTA_ROEMER_NPAR] */, double sign, int32_t separate,
+                           double* out);
+
 /* Replaces fakepta/fake_pta.py:201-230 (add_white_noise), with ECORR fixed (defects D1/D2):
  *   residuals[t] += sigma[t] * z[t]  +  sum over blocks b containing t: ecorr_sigma[b] * zb[b]
  * Blocks are CSR: block_offs[n_blocks+1] into block_idx (TOA indices, any order).
@@ -441,7 +489,8 @@ int fpta_build_flags(void);
 #define FPTA_K_DENSE 4 /* dense covariance: basis + Gram, Cholesky, solves, draws */
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
 #define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]) */
-#define FPTA_K_N 7
+#define FPTA_K_EPHEM 7 /* fpta_ephem_kepler / fpta_ephem_orbits / fpta_roemer_accumulate: one entry per call */
+#define FPTA_K_N 8
 /* Accumulated launches and HIP-event milliseconds of kernel `which` since the last reset. */
 int fpta_kernel_stats(fpta_ctx* ctx, int32_t which, int64_t* count, double* total_ms);
 int fpta_reset_stats(fpta_ctx* ctx);
