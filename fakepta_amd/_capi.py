@@ -68,6 +68,7 @@ _SIGS = [
     ("fpta_debug_philox", _c_int, [_ctx_p, _i64, _vp, _vp, _vp]),
     ("fpta_debug_normals", _c_int, [_ctx_p, _i64, _vp, _vp]),
     ("fpta_debug_fill_out", _c_int, [_ctx_p, _dbl]),
+    ("fpta_debug_fused_shape", _c_int, [_ctx_p, _vp]),
     ("fpta_get_option", _c_int, [_ctx_p, _i32, ctypes.POINTER(_i64)]),
     ("fpta_build_flags", _c_int, []),
     ("fpta_batch_path_reason", ctypes.c_char_p, [_ctx_p]),
@@ -93,7 +94,7 @@ _SIGS = [
 ]
 # entry points newer than an older library a same-box A/B may load through FAKEPTA_AMD_LIB (tools/gpu_ab_cfg.sh LIB=):
 # bound when present (the product library exports every one: tests/test_capi_symbols.py)
-_OPTIONAL = {"fpta_debug_normals"}
+_OPTIONAL = {"fpta_debug_normals", "fpta_debug_fused_shape"}
 for _name, _res, _args in _SIGS:
     try:
         _fn = getattr(_lib, _name)
@@ -518,6 +519,13 @@ class Context:
     def debug_fill_out(self, value):
         """Fill the last device block with `value` (tests: the next batch must overwrite every sample)."""
         self._check(_lib.fpta_debug_fill_out(self._h, float(value)), "fpta_debug_fill_out")
+
+    def debug_fused_shape(self):
+        """The variant of the reported k_grid_fused instance the last gridded block ran: 1 / 2 the instance of the
+        layout's draw shape (csrc/fused_sched.h), 0 the fallback, -1 no k_grid_fused."""
+        shape = np.zeros(1, dtype=np.int32)
+        self._check(_lib.fpta_debug_fused_shape(self._h, _ptr(shape)), "fpta_debug_fused_shape")
+        return int(shape[0])
 
     def debug_philox(self, ctr, key):
         ctr = np.ascontiguousarray(ctr, dtype=np.uint32).reshape(-1, 4)

@@ -1673,6 +1673,12 @@ extern "C" int fpta_debug_fused_prof(fpta_ctx* c, unsigned long long* host, int6
 }
 #endif
 
+int fpta_debug_fused_shape(fpta_ctx* c, int32_t* shape) {
+  if (!c || !shape) return fail(c, FPTA_EINVAL, "debug_fused_shape: bad arguments");
+  *shape = c->last_interp > 0 ? c->last_fused_shape : -1;
+  return FPTA_OK;
+}
+
 int fpta_debug_fill_out(fpta_ctx* c, double value) {
   if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
   if (!c->out_R) return fail(c, FPTA_ESTATE, "fill_out: nothing synthesized yet");

@@ -257,6 +257,8 @@ struct fpta_ctx {
   int overlap = 1;
   int interp_ws = 1;      // gridded interpolation on the warp-specialised kernel (FPTA_OPT_INTERP_WS)
   int last_interp = 0;    // interpolation kernel of the last gridded block: 1 + 4 kind + 2 white + part (0: none)
+  int last_fused_shape = -1;  // draw shape of the last gridded block's k_grid_fused instance (fused_sched.h; 0: the
+                              // fallback); -1: that block ran another kernel (fpta_debug_fused_shape)
   double last_fma_interp = 0.0;  // its interpolation MFMA FMAs per realization as run (half-chunk bands: both halves)
   int grid_coalesce = 1;  // gridded path: signals sharing w0 and the chromatic weight share one grid (FPTA_OPT_GRID_COALESCE)
   int part_group = kPartGroup;  // fused partial checksums: consecutive chunks per partial row (FPTA_OPT_PART_GROUP)

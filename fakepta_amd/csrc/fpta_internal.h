@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fused_sched.h"
+
 namespace fpta {
 
 // One GP signal ("segment") of a layout, as the kernels see it.
@@ -281,12 +283,14 @@ constexpr double kFusedJoinSafety = FPTA_FUSED_JOIN_SAFETY;  // FusedArgs::join_
 // nq_max: band steps of the widest chunk (vmax / 4; the kernel holds up to 12 steps' operands and takes a wider chunk's
 // in turns); lds_bytes: grids + ring + sync word; ev0 / ev1: timing events bound to the dispatch (hipExtLaunchKernel)
 // half: the HALF kernel on f.h (nq_max: band steps of the widest half); *kernel_out (optional): the instance launched,
-// fused_kernel_name's index
+// fused_kernel_name's index; *shape_out (optional): the draw shape of the instance launched (kFusedShapeAny: the
+// fallback; fpta_debug_fused_shape)
 hipError_t launch_grid_fused(hipStream_t st, const SynthArgs& a, const GridBand& band, const FusedArgs& f,
                              int32_t nq_max, size_t lds_bytes, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                             bool half = false, int* kernel_out = nullptr);
+                             bool half = false, int* kernel_out = nullptr, int* shape_out = nullptr);
 constexpr int kFusedKernels = 9;  // instances: {NQ 8, NQ 12} x {no draws, draws, draws from an odd realization},
-                                  // then HALF (NQ 8 per half) x the same three
+                                  // then HALF (NQ 8 per half) x the same three; each as its draw shape's variant
+                                  // (fused_sched.h) and as the fallback
 // Storer-wave variant: compute waves hand finished sums to storer waves through LDS; every block kind (white / ECORR
 // epilogue, partial checksums, accumulate) with R_pad a multiple of 128
 hipError_t launch_grid_interp_st(hipStream_t st, const SynthArgs& a, const GridBand& band, int32_t R_pad);

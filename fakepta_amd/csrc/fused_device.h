@@ -42,6 +42,7 @@ __device__ __forceinline__ double dpp_xor1(double x) {
 
 __device__ __forceinline__ void fused_barrier() { asm volatile("s_barrier" ::: "memory"); }  // no vmcnt(0) fence
 __device__ __forceinline__ void fused_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(15 | (3 << 14) | (7 << 4)); }
+__device__ __forceinline__ void fused_wait_vm0() { __builtin_amdgcn_s_waitcnt((7 << 4) | (15 << 8)); }  // vmcnt(0) alone
 
 // A workgroup's items come from its XCD's queue (workgroup b runs on XCD b % 8): the items of XCD x are a contiguous
 // range (the items of one pulsar run side by side on one XCD, whose L2 then holds the pulsar's weights), handed out

@@ -169,9 +169,14 @@ __device__ __forceinline__ void fused_mix_tile(const FusedMix& m, int k, int rg,
 // (FusedHalf): per band step of half h, A = the realization pair of the half's band row, B = the weight of TOA 16 h +
 // lr, two MFMAs (C2: 2 x 8 steps x 2 instead of 9 steps x 4 MFMAs per chunk); 8-byte stores (a lane holds TOAs lr
 // and 16 + lr of each realization).
-template <int NQ, bool ODD, bool GEN, bool HALF>
-__global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(SynthArgs a, GridBand band, FusedArgs f,
-                                                                             int32_t n_rb, int32_t n_items) {
+// SHAPE: the draw shape (fused_sched.h): which term slots of which signal are generated, loaded or absent. The body
+// of both kernels below: k_grid_fused<NQ, ODD, GEN, HALF> is the instance of the shape that ships with those draws
+// (GEN: C2's, else C4's), k_grid_fused_any the same instance for every other layout.
+template <int NQ, bool ODD, bool GEN, bool HALF, int SHAPE>
+__device__ __forceinline__ void grid_fused_body(const SynthArgs& a, const GridBand& band, const FusedArgs& f,
+                                                int32_t n_rb, int32_t n_items) {
+  static_assert(kFusedTerms == 2 && kFusedMaxSig == 2, "fused_shape_slot's slots and signals (c0, c1)");
+  static_assert(SHAPE == kFusedShapeAny || GEN == (SHAPE == kFusedShapeGenLoad), "a shape fixes whether terms are drawn");
   static_assert(kFusedReal == 32 && kFusedPitch == 32 && kFusedGroupModes * kFusedReal / 2 == 64 * kFusedDW,
                 "two realization tiles; one (mode, realization pair) of a 16-mode group per DFT lane");
   static_assert(!HALF || (NQ % 4 == 0 && kGridTT == 2 * kFusedHalfTT), "half bands: whole row groups, two halves");
@@ -516,16 +521,18 @@ __global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(Sy
     // the DFT waves are the item's critical path (the interpolation waves wait at barrier A): first claim on the SIMD's
     // issue slots, the interpolation waves fill the gaps (C2 kernel -3%)
     __builtin_amdgcn_s_setprio(FPTA_FUSED_DFT_PRIO);
+    constexpr int kNSig = fused_shape_nsig(SHAPE);  // a shape fixes the signal count
+    const int n_sig = kNSig ? kNSig : f.n_sig;
     int js = -1, jrc = 0;  // this wave's job: grid signal js, quarter-range rows 32 jrc .. 32 jrc + 31
     {
       int j = dw;
 #pragma unroll
       for (int s = 0; s < kFusedMaxSig; ++s) {
-        if (s < f.n_sig && js < 0 && j < f.s[s].n_rc) {
+        if (s < n_sig && js < 0 && j < f.s[s].n_rc) {
           js = s;
           jrc = j;
         }
-        if (s < f.n_sig) j -= f.s[s].n_rc;
+        if (s < n_sig) j -= f.s[s].n_rc;
       }
     }
     js = __builtin_amdgcn_readfirstlane(js);
@@ -543,15 +550,12 @@ __global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(Sy
                  (int)__hip_atomic_load(sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < epoch)
         __builtin_amdgcn_s_sleep(1);
     };
-    // groups of 16 modes (two 4-mode k-steps of both parities) of grid signal s
-    auto n_groups = [&](int nm) { return (((((nm + 1) >> 1) + 3) >> 2) + 1) >> 1; };
+    // groups of 16 modes of grid signal s; the iterations per item (iteration g draws group g + 1 of every signal that
+    // has one and runs group g's steps: fused_sched.h)
     int ng[kFusedMaxSig];
-    int n_it = 0;  // iterations per item: iteration g draws group g + 1 of every signal and runs group g's steps
 #pragma unroll
-    for (int s = 0; s < kFusedMaxSig; ++s) {
-      ng[s] = s < f.n_sig ? n_groups(f.s[s].nm) : 0;
-      n_it = max(n_it, ng[s]);
-    }
+    for (int s = 0; s < kFusedMaxSig; ++s) ng[s] = s < n_sig ? fused_groups(f.s[s].nm) : 0;
+    const int n_it = fused_iterations(ng[0], ng[1]);
     // this wave's job, hoisted: its table rows (parity 0 cos, t = lg, rows 32 jrc + 2 lr) and k-steps per parity
     const FusedSig& jf = f.s[js < 0 ? 0 : js];
     const int64_t jts = (int64_t)jf.ntq * jf.ldq, jld4 = 4 * (int64_t)jf.ldq;
@@ -561,15 +565,16 @@ __global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(Sy
       const int ln = lane_now();
       return jf.tq + (int64_t)(ln >> 4) * jf.ldq + 32 * jrc + 2 * (ln & 15);
     };
-    const int jnq0 = (((jf.nm + 1) >> 1) + 3) >> 2, jnq1 = ((jf.nm >> 1) + 3) >> 2;
-    const int jng = js < 0 ? 0 : (jnq0 + 1) >> 1;
+    const int jnq0 = fused_ksteps(jf.nm, 0), jnq1 = fused_ksteps(jf.nm, 1);
+    const int jng = js < 0 ? 0 : fused_groups(jf.nm);
     // [parity: 0 odd k, 1 even k][row tile h: rows 2 i + h][realization tile t]
     d4 C[2][2][2], S[2][2][2];
     // Group g of signal s: modes 16 g .. 16 g + 15 x realizations r0 .. r0 + 31, one (mode m, realization pair r) per
     // lane, k_grid_dft_gen's coefficient (grid_term_coefs: the same operations) in three parts:
-    //  draw_load: every term slot's inputs, two 16-byte loads each whatever the term (a fixed count keeps the compiler's
-    //             vmcnt waits for the table operands exact): a generated term's amplitude, a loaded term's columns;
-    //             issued with the tables of the steps before them, so the latencies overlap;
+    //  draw_load: the term slots' inputs, 16-byte loads: a generated term's amplitude pair, a loaded term's cos and sin
+    //             columns; issued with the tables of the steps before them, so the latencies overlap. The fallback
+    //             (kinds known at run time only) issues two loads per slot whatever the term: a fixed count keeps
+    //             the compiler's vmcnt waits for its table operands exact;
     //  draw_normals: the generated terms' normals (no memory);
     //  draw_store: amp * z (rounded) and the loaded values summed in the terms' order, into the ring.
     // The signal index is a constant wherever these run (loops over kFusedMaxSig unrolled): the descriptor's fields are
@@ -577,28 +582,48 @@ __global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(Sy
     struct DrawIn {
       dbl2 x0[kFusedTerms], x1[kFusedTerms];  // generated: x0.x amplitude pair; loaded: x0 cos pair, x1 sin pair
     };
-    auto draw_load = [&](const FusedSig& fs, int g, int p, int r0, DrawIn& in) {
+    // The signal index sc is an std::integral_constant (c0, c1).
+    std::integral_constant<int, 0> c0;
+    std::integral_constant<int, 1> c1;
+    auto draw_load = [&](auto sc, int g, int p, int r0, DrawIn& in) {
+      constexpr int s = decltype(sc)::value;
+      const FusedSig& fs = f.s[s];
       const int didx = dw * 64 + lane_now(), dmm = didx >> 4, drl = 2 * (didx & 15);
       const int m = kFusedGroupModes * g + dmm, r = r0 + drl;
-#pragma unroll
-      for (int i = 0; i < kFusedTerms; ++i) {
-        const bool on = i < fs.n_terms;
-        const int nmi = on ? fs.term_nm[i] : 2;
-        const int mi = min(m, nmi - 1);  // clamped: a mode past the term's is never used
-        const double* src0;
-        int64_t step;
-        if (on && fs.term_kind[i] == 1) {
-          src0 = a.coef + ((int64_t)p * a.K + fs.term_col0[i] + 2 * mi) * a.R_pad + r;
-          step = a.R_pad;
-        } else {  // the amplitude pair (mi, mi + 1) of a generated term: .x is amp[mi] (rows are padded to even nm)
-          src0 = (on ? fs.term_amp[i] : a.coef) + (int64_t)p * nmi + (mi & ~1);
-          step = 0;
+      auto slot = [&](auto ic) {
+        constexpr int i = decltype(ic)::value, kind = fused_shape_slot(SHAPE, s, i);
+        if constexpr (kind == kFusedSlotGen) {
+          // the amplitude pair (mi, mi + 1): .x is amp[mi] (rows are padded to even nm)
+          const int nmi = fs.term_nm[i], mi = min(m, nmi - 1);  // clamped: a mode past the term's is never used
+          in.x0[i] = ld_global((const dbl2*)(fs.term_amp[i] + (int64_t)p * nmi + (mi & ~1)));
+        } else if constexpr (kind == kFusedSlotLoad) {
+          const int mi = min(m, fs.term_nm[i] - 1);
+          const double* src0 = a.coef + ((int64_t)p * a.K + fs.term_col0[i] + 2 * mi) * a.R_pad + r;
+          in.x0[i] = ld_global((const dbl2*)src0);
+          in.x1[i] = ld_global((const dbl2*)(src0 + a.R_pad));
+        } else if constexpr (kind == kFusedSlotAny) {
+          const bool on = i < fs.n_terms;
+          const int nmi = on ? fs.term_nm[i] : 2;
+          const int mi = min(m, nmi - 1);
+          const double* src0;
+          int64_t step;
+          if (on && fs.term_kind[i] == 1) {
+            src0 = a.coef + ((int64_t)p * a.K + fs.term_col0[i] + 2 * mi) * a.R_pad + r;
+            step = a.R_pad;
+          } else {
+            src0 = (on ? fs.term_amp[i] : a.coef) + (int64_t)p * nmi + (mi & ~1);
+            step = 0;
+          }
+          in.x0[i] = ld_global((const dbl2*)src0);
+          in.x1[i] = ld_global((const dbl2*)(src0 + step));
         }
-        in.x0[i] = ld_global((const dbl2*)src0);
-        in.x1[i] = ld_global((const dbl2*)(src0 + step));
-      }
+      };
+      slot(c0);
+      slot(c1);
     };
-    auto draw_finish = [&](const FusedSig& fs, int g, int p, int r0, double* __restrict__ slot_s, const DrawIn& in) {
+    auto draw_finish = [&](auto sc, int g, int p, int r0, double* __restrict__ slot_s, const DrawIn& in) {
+      constexpr int s = decltype(sc)::value;
+      const FusedSig& fs = f.s[s];
       const int didx = dw * 64 + lane_now(), dmm = didx >> 4, drl = 2 * (didx & 15);
       const int m = kFusedGroupModes * g + dmm, r = r0 + drl;
       const uint64_t gr = (uint64_t)(f.real0 + r);
@@ -614,22 +639,27 @@ __global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(Sy
       };
       const bool ok0 = r < a.n_real, ok1 = r + 1 < a.n_real;  // padding realizations: zero, as k_gen writes them
       auto normals = [&](int seg, double (&z)[4]) {
+        // the key from opaque copies: Philox's twenty round keys (key + round x constant) are then scalar additions
+        // here, not values hoisted out of every loop that the compiler spills and reloads one per round (the shaped
+        // instances only: with it the fallback measured slower)
+        uint32_t k0 = f.k0, k1 = f.k1;
+        if (SHAPE != kFusedShapeAny) asm volatile("" : "+s"(k0), "+s"(k1));
         if (!ODD) {  // r0 and r are even: the first realization's parity is the launch's
-          gp_pair2((uint32_t)m, (uint32_t)p, (uint32_t)seg, gr, f.k0, f.k1, z);
+          gp_pair2((uint32_t)m, (uint32_t)p, (uint32_t)seg, gr, k0, k1, z);
         } else {
-          gp_normal2((uint32_t)m, (uint32_t)p, (uint32_t)seg, gr, f.k0, f.k1, z[0], z[1]);
-          gp_normal2((uint32_t)m, (uint32_t)p, (uint32_t)seg, gr + 1, f.k0, f.k1, z[2], z[3]);
+          gp_normal2((uint32_t)m, (uint32_t)p, (uint32_t)seg, gr, k0, k1, z[0], z[1]);
+          gp_normal2((uint32_t)m, (uint32_t)p, (uint32_t)seg, gr + 1, k0, k1, z[2], z[3]);
         }
         z[0] = ok0 ? z[0] : 0.0;
         z[1] = ok0 ? z[1] : 0.0;
         z[2] = ok1 ? z[2] : 0.0;
         z[3] = ok1 ? z[3] : 0.0;
       };
-#pragma unroll
-      for (int i = 0; i < kFusedTerms; ++i) {
-        if (i >= fs.n_terms) continue;
+      auto term = [&](auto ic) {
+        constexpr int i = decltype(ic)::value, kind = fused_shape_slot(SHAPE, s, i);
+        if (kind == kFusedSlotNone || (kind == kFusedSlotAny && i >= fs.n_terms)) return;
         double pc[2], ps[2];
-        if (GEN && fs.term_kind[i] == 0) {
+        if (kind == kFusedSlotGen || (kind == kFusedSlotAny && GEN && fs.term_kind[i] == 0)) {
           double z[4];
           normals(fs.term_seg[i], z);
           const double amp = (m & 1) ? in.x0[i].y : in.x0[i].x;
@@ -644,10 +674,12 @@ __global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(Sy
           ps[1] = in.x1[i].y;
         }
         add(m < fs.nm && m < fs.term_nm[i], pc, ps);
-      }
+      };
+      term(c0);
+      term(c1);
       // members past kFusedTerms (a grid signal of three or more, e.g. coalesced RN + DM + GWB at one radio frequency):
-      // loaded and drawn here, in order, with the same operations
-      for (int i = kFusedTerms; i < fs.n_terms; ++i) {
+      // loaded and drawn here, in order, with the same operations (the fallback only: no shape has them)
+      for (int i = kFusedTerms; SHAPE == kFusedShapeAny && i < fs.n_terms; ++i) {
         const int mi = min(m, fs.term_nm[i] - 1);
         double pc[2], ps[2];
         if (GEN && fs.term_kind[i] == 0) {
@@ -732,34 +764,62 @@ __global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(Sy
 #pragma unroll
           for (int t = 0; t < 2; ++t) C[par][h][t] = S[par][h][t] = d4{0.0, 0.0, 0.0, 0.0};
       if (k == 0) {
-#pragma unroll
-        for (int s = 0; s < kFusedMaxSig; ++s) {
-          if (s >= f.n_sig) continue;
+        auto first = [&](auto sc) {
+          constexpr int s = decltype(sc)::value;
+          if (s >= n_sig) return;
           DrawIn in;
-          draw_load(f.s[s], 0, p, r0, in);
-          draw_finish(f.s[s], 0, p, r0, slot_of(sb, s), in);
-        }
+          draw_load(sc, 0, p, r0, in);
+          draw_finish(sc, 0, p, r0, slot_of(sb, s), in);
+        };
+        first(c0);
+        first(c1);
         pf.lap(6);
         dsync();
         pf.lap(2);
       }
+      // A shaped instance issues only the loads the iteration reads (fused_sched.h), under wave-uniform branches and in
+      // this order: the draw loads first, the table loads last. The compiler's vmcnt wait for a load counts the loads
+      // issued after it; a branch with loads in it makes it take the smaller count of the two sides, so a conditional
+      // load delays nothing but the waits for loads issued BEFORE it. The steps, which run first, wait for the tables,
+      // the last loads issued (vmcnt 0 on every side), and the draws that follow them find their inputs landed: no
+      // wait is longer than with every load in place. (Ranges of iterations with the loads in straight-line bodies
+      // instead: three more copies of the steps, whose accumulators the compiler then spilled. DESIGN.md section 9.)
+      // The fallback loads all, the tables first, as it always did: an unused descriptor is a copy of the first, and
+      // the draw group is clamped.
+      // Invariant: exactly one dsync per iteration and n_it iterations per build on every DFT wave, whatever the wave
+      // steps or draws; the ring slots follow sb + g alone.
+      constexpr bool kAny = SHAPE == kFusedShapeAny;
       for (int g = 0; g < n_it; ++g) {
         const bool last = g + 1 == n_it;
         const int dp = last ? p1 : p, dr = last ? r1 : r0;
         Tabs tb;
-        tables(g, tb);
+        if (kAny) tables(g, tb);
         DrawIn in[kFusedMaxSig];
-#pragma unroll
-        for (int s = 0; s < kFusedMaxSig; ++s)  // an unused descriptor is a copy of the first
-          draw_load(f.s[s], last ? 0 : min(g + 1, max(ng[s], 1) - 1), dp, dr, in[s]);
+        auto load = [&](auto sc) {
+          constexpr int s = decltype(sc)::value;
+          if (kAny || (s < kNSig && fused_draw_loads(ng[s], g, last)))
+            draw_load(sc, last ? 0 : min(g + 1, max(ng[s], 1) - 1), dp, dr, in[s]);
+        };
+        load(c0);
+        load(c1);
+        if (!kAny && fused_steps(jng, g)) tables(g, tb);
         pf.lap(0);
-        if (g < jng) steps(sb + g, g, tb);
+        if (fused_steps(jng, g)) steps(sb + g, g, tb);
         pf.lap(1);
-#pragma unroll
-        for (int s = 0; s < kFusedMaxSig; ++s)
-          if (last ? nx && s < f.n_sig : g + 1 < ng[s])
-            draw_finish(f.s[s], last ? 0 : g + 1, dp, dr, slot_of(sb + g + 1, s), in[s]);
+        auto finish_draw = [&](auto sc) {
+          constexpr int s = decltype(sc)::value;
+          if (s < n_sig && fused_draws(ng[s], g, last, nx))
+            draw_finish(sc, fused_draw_group(g, last), dp, dr, slot_of(sb + g + 1, s), in[s]);
+        };
+        finish_draw(c0);
+        finish_draw(c1);
         pf.lap(6);
+        // Loads whose reader did not run (the tables of a k-step past the parity's, the draws of the last item's last
+        // iteration) landed long ago, but the compiler has seen no wait for them: across the loop's back edge it then
+        // guards their registers with counted waits between the next iteration's loads, which at run time count that
+        // iteration's own loads and hold each table pair until the oldest of them has landed. One wait here, when
+        // nothing is in flight, keeps the next iteration's loads back to back. (Not in the fallback: measured slower.)
+        if (!kAny) fused_wait_vm0();
         dsync();
         pf.lap(2);
         pf.count(5);
@@ -932,9 +992,35 @@ __global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(Sy
   if (wave < kFusedIW) finish();  // thread 0: after the last barrier, so after every fetch of the workgroup
 }
 
+template <int NQ, bool ODD, bool GEN, bool HALF>
+__global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused(SynthArgs a, GridBand band, FusedArgs f,
+                                                                             int32_t n_rb, int32_t n_items) {
+  grid_fused_body<NQ, ODD, GEN, HALF, GEN ? kFusedShapeGenLoad : kFusedShapeLoad>(a, band, f, n_rb, n_items);
+}
+template <int NQ, bool ODD, bool GEN, bool HALF>
+__global__ __launch_bounds__(64 * (kFusedIW + kFusedDW), 1) void k_grid_fused_any(SynthArgs a, GridBand band,
+                                                                                 FusedArgs f, int32_t n_rb,
+                                                                                 int32_t n_items) {
+  grid_fused_body<NQ, ODD, GEN, HALF, kFusedShapeAny>(a, band, f, n_rb, n_items);
+}
+
+#ifndef FPTA_FUSED_SHAPES
+#define FPTA_FUSED_SHAPES 1  // 0 (variant builds): every layout on the fallback instances, to measure them on C2 / C4
+#endif
+// the draw shape whose instance serves these descriptors (fused_sched.h)
+static int fused_shape_of(const FusedArgs& f) {
+  int32_t n_terms[kFusedMaxSig], kind[kFusedMaxSig][2];
+  for (int s = 0; s < kFusedMaxSig; ++s) {
+    n_terms[s] = f.s[s].n_terms;
+    kind[s][0] = f.s[s].term_kind[0];
+    kind[s][1] = f.s[s].term_kind[1];
+  }
+  return FPTA_FUSED_SHAPES ? fused_shape_match(f.n_sig, n_terms, kind) : kFusedShapeAny;
+}
+
 hipError_t launch_grid_fused(hipStream_t st, const SynthArgs& a, const GridBand& band, const FusedArgs& f,
                              int32_t nq_max, size_t lds_bytes, hipEvent_t ev0, hipEvent_t ev1, bool half,
-                             int* kernel_out) {
+                             int* kernel_out, int* shape_out) {
   if (band.n_chunks <= 0 || band.vmax < 4 || f.join_reserve < 0 || band.vmax % 4 != 0 || a.R_pad % kFusedReal != 0 || a.w_on ||
       a.accumulate || a.part || !f.lrows || !f.psr_c0 || f.n_sig <= 0 || f.n_sig > kFusedMaxSig ||
       lds_bytes > (size_t)kFusedLdsMax || nq_max <= 0 || f.ring_off < 0 || f.fq < kFusedNQ || f.fq % 4 != 0 ||
@@ -948,7 +1034,7 @@ hipError_t launch_grid_fused(hipStream_t st, const SynthArgs& a, const GridBand&
   int jobs = 0;
   for (int s = 0; s < f.n_sig; ++s) {
     const FusedSig& fs = f.s[s];
-    const int nq = ((((fs.nm + 1) >> 1) + 3) >> 2);  // k-steps of the odd-k parity (the larger)
+    const int nq = fused_ksteps(fs.nm, 0);  // k-steps of the odd-k parity (the larger)
     if (fs.nf % 4 != 0 || !fs.tq || fs.n_rc != (fs.nf / 4 + 32) / 32 || fs.ldq < 32 * fs.n_rc || 4 * nq > fs.ntq ||
         fs.n_terms <= 0 || fs.n_terms > kDftGenTerms || fs.lrow0 < 0 || (fs.lrow0 + fs.nf) * kFusedPitch > f.ring_off)
       return hipErrorInvalidValue;
@@ -976,7 +1062,7 @@ hipError_t launch_grid_fused(hipStream_t st, const SynthArgs& a, const GridBand&
   // per device (one process may drive several devices from several threads, fpta_multi_*): its CU count, and whether
   // each instance's dynamic LDS limit is raised past 64 KB
   static std::atomic<int> n_cus[64];
-  static std::atomic<bool> attr_set[64][kFusedKernels];
+  static std::atomic<bool> attr_set[64][2][kFusedKernels];
   int n_cu = n_cus[dev].load(std::memory_order_relaxed);
   if (n_cu <= 0) {
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
@@ -994,16 +1080,24 @@ hipError_t launch_grid_fused(hipStream_t st, const SynthArgs& a, const GridBand&
   const bool odd = gen && (f.real0 & 1);
   const int ki = half ? 6 + (gen ? 1 + odd : 0) : (nq_max <= 8 ? 0 : 3) + (gen ? 1 + odd : 0);
   using K = void (*)(SynthArgs, GridBand, FusedArgs, int32_t, int32_t);
-  static const K kernels[kFusedKernels] = {
-      k_grid_fused<8, false, false, false>,  k_grid_fused<8, false, true, false>,  k_grid_fused<8, true, true, false>,
-      k_grid_fused<12, false, false, false>, k_grid_fused<12, false, true, false>, k_grid_fused<12, true, true, false>,
-      k_grid_fused<kFusedHalfNQ, false, false, true>, k_grid_fused<kFusedHalfNQ, false, true, true>,
-      k_grid_fused<kFusedHalfNQ, true, true, true>};
-  const K kernel = kernels[ki];
-  if (!attr_set[dev][ki].load(std::memory_order_acquire)) {
+  static const K kernels[2][kFusedKernels] = {
+      {k_grid_fused_any<8, false, false, false>, k_grid_fused_any<8, false, true, false>,
+       k_grid_fused_any<8, true, true, false>, k_grid_fused_any<12, false, false, false>,
+       k_grid_fused_any<12, false, true, false>, k_grid_fused_any<12, true, true, false>,
+       k_grid_fused_any<kFusedHalfNQ, false, false, true>, k_grid_fused_any<kFusedHalfNQ, false, true, true>,
+       k_grid_fused_any<kFusedHalfNQ, true, true, true>},
+      {k_grid_fused<8, false, false, false>, k_grid_fused<8, false, true, false>, k_grid_fused<8, true, true, false>,
+       k_grid_fused<12, false, false, false>, k_grid_fused<12, false, true, false>, k_grid_fused<12, true, true, false>,
+       k_grid_fused<kFusedHalfNQ, false, false, true>, k_grid_fused<kFusedHalfNQ, false, true, true>,
+       k_grid_fused<kFusedHalfNQ, true, true, true>}};
+  // the instance of the layout's draw shape (the shape of a GEN instance is C2's, of the others C4's), else the
+  // fallback: the same instance index, so the same reported name
+  const int shaped = fused_shape_of(f) == (gen ? kFusedShapeGenLoad : kFusedShapeLoad) ? 1 : 0;
+  const K kernel = kernels[shaped][ki];
+  if (!attr_set[dev][shaped][ki].load(std::memory_order_acquire)) {
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kFusedLdsMax);
     if (e != hipSuccess) return e;
-    attr_set[dev][ki].store(true, std::memory_order_release);
+    attr_set[dev][shaped][ki].store(true, std::memory_order_release);
   }
   // unused descriptors are copies of the first: the kernel's unconditional draw loads read valid memory through them
   FusedArgs fa = f;
@@ -1016,6 +1110,7 @@ hipError_t launch_grid_fused(hipStream_t st, const SynthArgs& a, const GridBand&
   const hipError_t e = hipExtLaunchKernel((const void*)kernel, dim3((unsigned)grid),
                                           dim3(64 * (kFusedIW + kFusedDW)), args, lds_bytes, st, ev0, ev1, 0);
   if (e == hipSuccess && kernel_out) *kernel_out = ki;
+  if (e == hipSuccess && shape_out) *shape_out = shaped ? (gen ? kFusedShapeGenLoad : kFusedShapeLoad) : kFusedShapeAny;
   return e;
 }
 

@@ -994,7 +994,7 @@ int grid_run(fpta_ctx* c, Layout& L, SynthArgs& a, int32_t R_pad, bool pipe) {
       int it_max = 0, gen = 0;
       for (int32_t s = 0; s < f.n_sig; ++s) {
         const int nm = f.s[s].nm;
-        it_max = std::max(it_max, (((((nm + 1) >> 1) + 3) >> 2) + 1) >> 1);
+        it_max = std::max(it_max, fused_groups(nm));
         for (int i = 0; i < f.s[s].n_terms; ++i) gen += f.s[s].term_kind[i] == 0;
       }
       const double build = it_max * (32.0 + 20.0 * gen);
@@ -1070,7 +1070,8 @@ int grid_run(fpta_ctx* c, Layout& L, SynthArgs& a, int32_t R_pad, bool pipe) {
     }
     hipEvent_t e0 = kt.start_ev();
     int ki = 0;
-    HIPCHK(c, kt.checked(launch_grid_fused(c->stream, a, band, f, nq, G.fused_lds, e0, kt.stop_ev(), half, &ki)),
+    HIPCHK(c, kt.checked(launch_grid_fused(c->stream, a, band, f, nq, G.fused_lds, e0, kt.stop_ev(), half, &ki,
+                                           &c->last_fused_shape)),
            "k_grid_fused launch");
     kind = kInterpKindFused0 + ki;  // fpta_batch_grid_info_n slot 15: the instance launched
     if (f.mix.n_tiles > 0) {
@@ -1113,6 +1114,7 @@ int grid_run(fpta_ctx* c, Layout& L, SynthArgs& a, int32_t R_pad, bool pipe) {
     HIPCHK(c, launch_grid_interp_mfma(c->stream, a, band, R_pad), "k_grid_interp_mfma launch");
   }
   c->last_interp = 1 + kind * 4 + (a.w_on ? 2 : 0) + (a.part ? 1 : 0);
+  if (kind < kInterpKindFused0) c->last_fused_shape = -1;
   if (kind < kInterpKindFused0) c->last_fma_interp = G.fma_interp;
   if (pipe) {  // buffer gi is free once this interpolation is done; the next block's DFT writes the other one
     HIPCHK(c, hipEventRecord(c->ev_gfree[gi], c->stream), "event record");

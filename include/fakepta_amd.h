@@ -505,6 +505,11 @@ int fpta_debug_philox(fpta_ctx* ctx, int64_t n, const uint32_t* ctr, const uint3
 int fpta_debug_normals(fpta_ctx* ctx, int64_t n, const uint32_t* words, double* out);
 /* Fill the last synthesized device block with `value` (tests: a later batch must overwrite every sample). */
 int fpta_debug_fill_out(fpta_ctx* ctx, double value);
+/* Which variant of the reported k_grid_fused instance the last gridded block ran (the name fpta_batch_grid_info_n
+ * slot 15 reports is the same for both): *shape = 1 or 2, the instance specialised for the layout's term pattern
+ * (1: grid signal 0 = a per-pulsar + a common member and signal 1 = a per-pulsar member; 2: one grid signal of one
+ * common member); 0, the general instance; -1, the block ran no k_grid_fused. Additive (tests). */
+int fpta_debug_fused_shape(fpta_ctx* ctx, int32_t* shape);
 
 #ifdef __cplusplus
 }
