@@ -79,106 +79,60 @@ struct GridSeg {
 // fpta_batch_grid_info_n slot 15 (1 + 4 kind + 2 white + part): kinds 0 .. 10 the interpolation kernels
 // (_capi.interp_kernel_name), kInterpKindFused0 + i k_grid_fused instance i of launch_grid_fused's table
 constexpr int kInterpKindFused0 = 11;
-struct GridPlan {
+struct GridPlan : PlanFigures {  // the plan's host-side figures: grid_plan.h
   bool built = false;
-  bool ok = false;           // usable for this layout (harmonic, <= kGridMaxSeg signals)
-  std::string why;           // reason when !ok
   int32_t w = 0;             // kernel width (grid cells)
   double sigma = 0.0;        // oversampling
   int32_t n_chunks = 0;
   DevBuf chunks;             // int4 {pulsar, first TOA (pulsar-local), count, band rows V (multiple of 4)}
-  int32_t vmax = 0;          // largest V: row pitch of the row-index and weight tables
-  int64_t grid_rows = 0;     // rows of the grid buffer: sum over signals of P nf
   DevBuf rows;               // [n_chunks][vmax] int32 grid-buffer row of each band row (all signals back to back)
   DevBuf wd;                 // [n_chunks][vmax][kGridTT] interpolation weights (chromatic factor, mask folded in)
   DevBuf g, g2;              // [grid_rows][R_pad] grid values of the batch (two buffers when pipelined)
-  std::vector<int32_t> psr_chunk0;  // [P + 1] first chunk of each pulsar (chunks are pulsar-major)
   // partial-checksum groups (FPTA_OPT_FUSE_CHECKSUMS): <= pg_size consecutive chunks of one pulsar each; pgfirst
   // [n_pg + 1] the first chunk of each group, psr_pg [P + 1] the first group of each pulsar
   int32_t pg_size = 0, n_pg = 0;
   DevBuf pgfirst, psr_pg;
   DevBuf psr_c0;  // device copy of psr_chunk0 (k_grid_interp_psr without partial checksums)
-  // k_grid_fused plan (FPTA_OPT_INTERP_FUSED): every grid signal's grid for kFusedReal realizations in LDS (signal s
-  // at LDS row fused_lrow0[s]), the draw ring after them; frows [n_chunks][vmax] the LDS row of each band row;
-  // fused_lds the workgroup's LDS bytes
-  bool fused_ok = false;
-  size_t fused_lds = 0;
-  int32_t fused_fq = 0;  // band steps per (chunk, lane group) in frows
-  std::vector<int32_t> fused_lrow0;
-  DevBuf frows;
+  DevBuf frows;  // k_grid_fused: [n_chunks][4][fused_fq] the LDS row of each band row
   // half-chunk bands of the fused kernel (FusedHalf): hchunks {pulsar, first TOA, count, nq0 | nq1 << 16}, hrows
-  // [n_chunks][2][4][fused_hfq], hwd [2 n_chunks][fused_hvmax][16] (+ padding); fused_half_gain = the interpolation
-  // MFMAs of whole-chunk bands over those of half-chunk bands
-  bool fused_half_ok = false;
-  int32_t fused_hfq = 0, fused_hvmax = 0, fused_hnq = 0;
-  double fused_half_gain = 0.0;
-  double fma_interp_half = 0.0;  // interpolation FMAs per realization on half-chunk bands (both halves run max(nq0, nq1) steps)
+  // [n_chunks][2][4][fused_hfq], hwd [2 n_chunks][fused_hvmax][16] (+ padding)
   DevBuf hchunks, hrows, hwd;
-  // k_grid_interp_wr plan (GridWindow): <= 2 grid signals, each signal's band rows in a ring of kWrSlots LDS slots by
-  // unwrapped row; per chunk the slot of each band row, and the rows to load: all its band rows (full) or those not in
-  // the previous chunk's band (new; = full and flagged fresh when the two bands do not fit one ring window)
-  bool wr_ok = false;
-  DevBuf wr_meta, wr_list, wr_slot;
-  // k_grid_interp_lds plan: groups int4 {first chunk, chunks, union rows U, offset into urows}; urows the grid-
-  // buffer rows of each group's union; lrows [n_chunks][vmax] the union slot of each band row
-  bool lds_ok = false;
-  int32_t n_groups = 0, lds_rows = 0;
-  DevBuf groups, urows, lrows;
-  // k_grid_interp_u plan (GridUnion): groups of <= kUnionGroup chunks with <= kUnionRowsMax union rows; per chunk the
-  // signals' band offsets and union bases; per (chunk, signal, TOA slot) the window's first band row and {d, ch}
-  bool u_ok = false;
-  int32_t u_groups = 0, u_sig = 0;
-  DevBuf ugroups, uurows, ucbase, udch, uwrow;
-  int32_t u_w[kUnionSigMax] = {0, 0};
-  double u_hw[kUnionSigMax] = {0.0, 0.0}, u_beta[kUnionSigMax] = {0.0, 0.0};
+  // The diagnostic kernels' plans (diag/grid_plan_diag.h): made in variant builds only, cleared in the product library
+  struct Diag {
+    // k_grid_interp_wr plan (GridWindow): <= 2 grid signals, each signal's band rows in a ring of kWrSlots LDS slots by
+    // unwrapped row; per chunk the slot of each band row, and the rows to load: all its band rows (full) or those not
+    // in the previous chunk's band (new; = full and flagged fresh when the two bands do not fit one ring window)
+    bool wr_ok = false;
+    DevBuf wr_meta, wr_list, wr_slot;
+    // k_grid_interp_lds plan: groups int4 {first chunk, chunks, union rows U, offset into urows}; urows the grid-
+    // buffer rows of each group's union; lrows [n_chunks][vmax] the union slot of each band row
+    bool lds_ok = false;
+    int32_t n_groups = 0, lds_rows = 0;
+    DevBuf groups, urows, lrows;
+    // k_grid_interp_u plan (GridUnion): groups of <= kUnionGroup chunks with <= kUnionRowsMax union rows; per chunk the
+    // signals' band offsets and union bases; per (chunk, signal, TOA slot) the window's first band row and {d, ch}
+    bool u_ok = false;
+    int32_t u_groups = 0, u_sig = 0;
+    DevBuf ugroups, uurows, ucbase, udch, uwrow;
+    int32_t u_w[kUnionSigMax] = {0, 0};
+    double u_hw[kUnionSigMax] = {0.0, 0.0}, u_beta[kUnionSigMax] = {0.0, 0.0};
+    void clear() {
+      wr_ok = lds_ok = u_ok = false;
+      n_groups = lds_rows = u_groups = u_sig = 0;
+    }
+  } diag;
   std::vector<GridSeg*> segs;  // one per grid signal
-  // grid signals (FPTA_OPT_GRID_COALESCE): members (layout signal indices, ascending), the anchor (the member with
-  // the most modes: its coefficient columns receive the others' and its grid/weights serve the group) and the last
-  // member (the group's coefficients are complete once it is drawn)
-  std::vector<std::vector<int32_t>> members;
-  std::vector<int32_t> anchor, last;
-  bool merges = false;       // some grid signal has > 1 member
-  double mean_v = 0.0;       // mean band rows per chunk
-  double fma_grid = 0.0;     // FMAs per realization: DFT + interpolation
-  double fma_dft = 0.0;      // FMAs per realization in k_grid_dft
-  double fma_interp = 0.0;   // FMAs per realization in k_grid_interp (dense band, padded TOA slots)
-  double grid_vals = 0.0;    // grid values per realization (sum over signals of P nf)
-  double weight_bytes = 0.0; // interpolation weight tables
-  double fma_direct = 0.0;   // FMAs per realization of the direct contraction
-  double err_bound = 1.0;    // a-priori relative aliasing bound of the ES kernel, exp(-pi w sqrt(1 - 1/sigma))
   int64_t g_rpad = 0;        // R_pad the grid buffers are sized for
   ~GridPlan() { clear(); }
   void clear() {
     for (GridSeg* g : segs) delete g;
     segs.clear();
-    built = ok = false;
+    static_cast<PlanFigures&>(*this) = PlanFigures();
+    built = false;
     n_chunks = 0;
-    vmax = 0;
-    lds_ok = false;
-    n_groups = lds_rows = 0;
-    u_ok = false;
-    u_groups = u_sig = 0;
-    grid_rows = 0;
+    diag.clear();
     g_rpad = 0;
-    psr_chunk0.clear();
     pg_size = n_pg = 0;
-    wr_ok = false;
-    fused_ok = false;
-    fused_lds = 0;
-    fused_lrow0.clear();
-    fused_half_ok = false;
-    fused_hfq = fused_hvmax = fused_hnq = 0;
-    fused_half_gain = 0.0;
-    fma_interp_half = 0.0;
-    members.clear();
-    anchor.clear();
-    last.clear();
-    merges = false;
-    mean_v = 0.0;
-    // the plan figures accumulate over signals in grid_build: a rebuilt plan must start from zero
-    fma_grid = fma_dft = fma_interp = grid_vals = weight_bytes = fma_direct = 0.0;
-    err_bound = 1.0;
-    why.clear();
   }
 };
 

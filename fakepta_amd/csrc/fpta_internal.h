@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "fused_sched.h"
+#include "grid_plan.h"
 
 namespace fpta {
 
@@ -82,17 +83,9 @@ constexpr int kNumValuVariants = sizeof(kValuVariants) / sizeof(kValuVariants[0]
 constexpr ValuVariant kSeededVariants[] = {{1, 16}, {2, 16}, {1, 8}, {2, 8}, {1, 32}, {4, 16}};
 static_assert(sizeof(kSeededVariants) == sizeof(kValuVariants), "one variant index selects both tables");
 
-// Gridded synthesis (grid.hip): one signal's tables as the kernels see them.
-constexpr int kGridVMax = 256;  // band rows per chunk, all signals (k_grid_interp_mfma keeps them in 4 VGPRs)
-constexpr int kGridMinV = 16;  // band rows per chunk at least (k_grid_interp_st: 4 MFMA steps, its lookahead + 1)
-constexpr int kGridTT = 32;  // TOAs per interpolation chunk (k_grid_interp_mfma: even / odd TOAs = two MFMA B-tiles)
+// Gridded synthesis (grid.hip): one signal's tables as the kernels see them. The constants the plan of a layout
+// depends on (kGridTT, kGridVMax, kGridDftRows, kFused*, ...) are grid_plan.h's.
 constexpr int kGridMI = 8;   // grid rows per wave in k_grid_dft
-#ifndef FPTA_DFT_MJ
-#define FPTA_DFT_MJ 2
-#endif
-constexpr int kDftMJ = FPTA_DFT_MJ;      // k_grid_dft_mfma wave tile: 16 MJ grid rows x 16 kDftMR realizations
-constexpr int kDftMR = 4 / FPTA_DFT_MJ;  // (the accumulators stay at 4 MJ MR = 16 tiles: two parities, cos and sin)
-constexpr int kGridDftRows = 16 * kDftMJ;  // grid rows per k_grid_dft_mfma row block (quarter range) and k_grid_dft (half)
 struct GridSegDev {
   const double* ecos;  // [nm][lde] q_k cos(2 pi k j / nf), k = m + 1 (zero-padded columns)
   const double* esin;  // [nm][lde] q_k sin(2 pi k j / nf)
@@ -104,7 +97,6 @@ struct GridSegDev {
                        // odd k (m = 2 t) and of even k (m = 2 t + 1), t < ntq (zero-padded)
   int32_t ldq, ntq;
 };
-constexpr int kGridMaxSeg = 16;  // signals per layout on the gridded path (passed by value as kernel arguments)
 struct GridSegs {
   GridSegDev s[kGridMaxSeg];
   int32_t n;
@@ -133,7 +125,6 @@ hipError_t launch_grid_dft_mfma(hipStream_t st, GridSegs gsegs, int32_t P, const
 // members in layout order): a per-pulsar member's coefficient amp * z from its own Philox stream (the k_gen counter
 // {mode, pulsar, signal, realization}: the same draws), a common member's mixed coefficients loaded from its own
 // columns of the coefficient buffer. No k_gen launch and no coefficient round trip for per-pulsar members.
-constexpr int kDftGenTerms = 8;
 struct DftGenArgs {
   GridSegDev g;             // the grid signal's tables and its block of the grid buffer (nm: the anchor's modes)
   int32_t n_terms;
@@ -173,9 +164,7 @@ hipError_t launch_grid_interp_ws(hipStream_t st, const SynthArgs& a, const GridB
 // grid signal's band rows stay in a ring of kWrSlots LDS rows (slot = unwrapped row mod kWrSlots), so producer waves
 // load only the rows the previous chunk's band did not hold, plus the chunk's weights; one barrier per chunk (two
 // when the bands do not fit one window). Plain blocks, <= kWrMaxSig grid signals, R_pad a multiple of 256.
-constexpr int kWrSlots = 32, kWrMaxSig = 2, kWrVMax = 40, kWrReal = 256;  // 128 + 30 KB of LDS
-constexpr int kWrFresh = 1 << 30;  // GridWindow::meta .w flag: load every band row, after the previous chunk is done
-constexpr int kWrFar = 1 << 29;    // .w flag: the new rows may load only once the chunk two back is done
+constexpr int kWrReal = 256;        // kWrSlots, kWrMaxSig, kWrVMax (grid_plan.h): 128 + 30 KB of LDS
 constexpr int kWrBufs = 3;         // weight buffers: the chunk being computed, the next one, the one after
 struct GridWindow {
   const int4* meta;    // [n_chunks] {full list offset, full count, new list offset, new count | kWrFresh}
@@ -196,18 +185,10 @@ hipError_t launch_grid_interp_psr(hipStream_t st, const SynthArgs& a, const Grid
 // 32-row chunk each); kFusedIW interpolation waves meanwhile interpolate the previous item's chunks from its LDS grid
 // (k_grid_interp_ws's MFMA steps). At the item boundary the DFT waves write the next grid. No grid buffer, no DFT
 // launch; bit-identical to the two-kernel path.
-constexpr int kFusedMaxSig = 2;    // grid signals (the draw ring holds a group of each)
-constexpr int kFusedReal = 32;     // realizations per item (two 16-realization MFMA tiles)
-constexpr int kFusedPitch = 32;    // doubles per LDS grid row
+// (kFusedMaxSig, kFusedReal, kFusedPitch, kFusedDW, kFusedSlot, kFusedLdsMax, kFusedFqMin, kFusedPadRows: grid_plan.h)
 constexpr int kFusedIW = 4;        // interpolation waves per workgroup
-constexpr int kFusedDW = 4;        // DFT waves per workgroup = DFT jobs (32-row quarter-range chunks) at most
-constexpr int kFusedGroupModes = 16;  // modes per draw group: two 4-mode k-steps of both parities
-constexpr int kFusedSlot = kFusedGroupModes * kFusedReal * 2;  // doubles per signal of a ring slot [16 modes][32][cos, sin]
-constexpr int kFusedLdsMax = 160 * 1024;
 constexpr int kFusedNQ = 12;       // band steps whose operands an interpolation wave holds (a wider chunk: the rest one
                                    // step at a time)
-constexpr int kFusedFqMin = 16;    // floor of FusedArgs::fq: padding k_grid_fused's unconditional band-step loads rely on
-constexpr int kFusedPadRows = 4 * kFusedFqMin;  // zero-weight band rows past the last chunk (GridPlan::wd): the same padding
 constexpr int kFusedTerms = 2;     // members of a grid signal whose inputs the DFT waves prefetch (the others: inline)
 struct FusedSig {
   const double* tq;  // quarter-range tables [4][ntq][ldq] (GridSegDev::tq)
@@ -225,8 +206,6 @@ struct FusedSig {
 // (C2: 32 instead of 36 band rows per chunk and half, 11 % fewer interpolation MFMAs). A half's weights are [vmax_h][16
 // TOAs], laid out by pairs of band steps so that lane (TOA tt, row group j) reads steps 2 qp and 2 qp + 1 of band rows
 // 4 q + j with one 16-byte load: element (v, tt) at ((v / 8 * 4 + v % 4) * 16 + tt) * 2 + (v / 4) % 2.
-constexpr int kFusedHalfTT = 16;
-constexpr int kFusedHalfNQ = 8;  // band steps of each half whose operands an interpolation wave holds
 __host__ __device__ __forceinline__ int64_t fused_half_weight_index(int32_t v, int32_t tt) {
   return ((int64_t)((v >> 3) * 4 + (v & 3)) * kFusedHalfTT + tt) * 2 + ((v >> 2) & 1);
 }
@@ -296,7 +275,6 @@ constexpr int kFusedKernels = 9;  // instances: {NQ 8, NQ 12} x {no draws, draws
 hipError_t launch_grid_interp_st(hipStream_t st, const SynthArgs& a, const GridBand& band, int32_t R_pad);
 // LDS-staged variant: the 4 waves of a workgroup take <= kLdsGroup consecutive chunks of one pulsar for the same
 // realizations; the union of their band rows (<= kLdsRowsMax) is loaded once into LDS
-constexpr int kLdsGroup = 4, kLdsRowsMax = 144;
 struct GridLds {
   const int4* groups;   // [n_groups] {first chunk, chunks, union rows U, offset into urows}
   const int32_t* urows; // grid-buffer rows of each group's union
@@ -309,7 +287,7 @@ hipError_t launch_grid_interp_lds(hipStream_t st, const SynthArgs& a, const Grid
 // pulsar for 128 realizations, stages the union of their band rows (<= kUnionRowsMax rows over all signals) in LDS
 // once, and each compute wave interpolates one chunk from it with its weights made on the fly (es_weight); layouts of
 // <= kUnionSigMax grid signals.
-constexpr int kUnionGroup = 4, kUnionRowsMax = 76, kUnionSigMax = 2, kUnionPitch = 130;
+constexpr int kUnionPitch = 130;
 struct GridUnion {
   const int4* groups;    // [n_groups] {first chunk, chunks, union rows U, offset into urows}
   const int32_t* urows;  // grid-buffer rows of each group's union (signal by signal)

@@ -5,34 +5,60 @@
 namespace __attribute__((visibility("hidden"))) capi {  // library-internal: not exported
 
 // ------------------------------------------------------------------------------- gridded plan
-// Gauss-Legendre nodes/weights on [-1, 1] (Newton on P_n; host, once per plan).
-void gauss_legendre(int n, std::vector<double>& x, std::vector<double>& wt) {
-  x.assign(n, 0.0);
-  wt.assign(n, 0.0);
-  for (int i = 0; i < (n + 1) / 2; ++i) {
-    double z = std::cos(M_PI * (i + 0.75) / (n + 0.5)), dp = 1.0;
-    for (int it = 0; it < 100; ++it) {
-      double p0 = 1.0, p1 = z;
-      for (int k = 2; k <= n; ++k) {
-        const double p2 = ((2.0 * k - 1.0) * z * p1 - (k - 1.0) * p0) / k;
-        p0 = p1;
-        p1 = p2;
-      }
-      dp = n * (z * p1 - p0) / (z * z - 1.0);
-      const double dz = p1 / dp;
-      z -= dz;
-      if (std::fabs(dz) < 1e-16) break;
-    }
-    x[i] = -z;
-    x[n - 1 - i] = z;
-    wt[i] = wt[n - 1 - i] = 2.0 / ((1.0 - z * z) * dp * dp);
-  }
-}
+// The plan itself is plain C++ (grid_plan.h: plan_grid and its stages); here it is uploaded.
+static_assert(sizeof(Int4) == sizeof(int4) && offsetof(Int4, y) == offsetof(int4, y) &&
+                  offsetof(Int4, z) == offsetof(int4, z) && offsetof(Int4, w) == offsetof(int4, w),
+              "Int4 tables are uploaded as int4");
 
-// Build the gridded plan (grid.hip) of layout L: per signal the grid size nf, the deconvolved real-DFT
-// table, the chunking of every pulsar's TOAs into runs of <= kGridTT whose interpolation rows span at
-// most kGridRowCap cells, and the dense banded weights (device). Not usable -> ok = false + why.
-constexpr int kGridRowCap = 48;
+#ifdef FPTA_DIAG_KERNELS
+}  // namespace capi
+#include "diag/grid_plan_diag.h"
+namespace __attribute__((visibility("hidden"))) capi {
+static_assert(sizeof(Int2) == sizeof(int2) && offsetof(Int2, y) == offsetof(int2, y), "uploaded as int2");
+
+// The window-ring, LDS-union and union-row plans of the diagnostic kernels, made from plan H and uploaded.
+static int grid_build_diag(fpta_ctx* c, GridPlan::Diag& D, const HostGridPlan& H) {
+  const DiagWindowPlan W = plan_diag_window(H);
+  const DiagLdsPlan S = plan_diag_lds(H);
+  const DiagUnionPlan U = plan_diag_union(H);
+  int rc;
+  D.wr_ok = W.ok;
+  if (W.ok && ((rc = upload(c, D.wr_meta, W.meta.data(), sizeof(int4) * W.meta.size(), "window plan")) ||
+               (rc = upload(c, D.wr_list, W.list.data(), sizeof(int2) * std::max<size_t>(W.list.size(), 1),
+                            "window rows")) ||
+               (rc = upload(c, D.wr_slot, W.slot.data(), sizeof(int32_t) * W.slot.size(), "window slots"))))
+    return rc;
+  D.lds_ok = S.ok;
+  D.n_groups = (int32_t)S.groups.size();
+  D.lds_rows = S.lds_rows;
+  if (S.ok && ((rc = upload(c, D.groups, S.groups.data(), sizeof(int4) * S.groups.size(), "grid groups")) ||
+               (rc = upload(c, D.urows, S.urows.data(), sizeof(int32_t) * S.urows.size(), "grid union rows")) ||
+               (rc = upload(c, D.lrows, S.lrows.data(), sizeof(int32_t) * S.lrows.size(), "grid LDS rows"))))
+    return rc;
+  D.u_ok = U.ok;
+  D.u_groups = (int32_t)U.groups.size();
+  D.u_sig = H.n_seg();
+  if (U.ok) {
+    for (int32_t s = 0; s < H.n_seg(); ++s) {
+      D.u_w[s] = H.segs[s].w;
+      D.u_hw[s] = 0.5 * (double)H.segs[s].w;
+      D.u_beta[s] = H.segs[s].beta;
+    }
+    if ((rc = upload(c, D.ugroups, U.groups.data(), sizeof(int4) * U.groups.size(), "union groups")) ||
+        (rc = upload(c, D.uurows, U.urows.data(), sizeof(int32_t) * U.urows.size(), "union rows")) ||
+        (rc = upload(c, D.ucbase, U.cbase.data(), sizeof(int32_t) * U.cbase.size(), "union bases")) ||
+        (rc = upload(c, D.uwrow, U.wrow.data(), sizeof(int32_t) * U.wrow.size(), "union window rows")))
+      return rc;
+    const size_t dbytes = sizeof(double) * 2 * (size_t)H.n_chunks() * H.n_seg() * kGridTT;
+    HIPCHK(c, D.udch.ensure(dbytes), "union weight parameters alloc");
+    HIPCHK(c, hipMemsetAsync(D.udch.p, 0, dbytes, c->stream), "union weight parameters memset");
+  }
+  return FPTA_OK;
+}
+#endif
+
+// Build the gridded plan (grid.hip) of layout L: plan_grid on a host view of L, its tables uploaded, and the dense
+// banded weights made on the device (k_grid_weights). Not usable -> ok = false + why.
 int grid_build(fpta_ctx* c, Layout& L) {
   GridPlan& G = L.grid;
   if (G.built && G.w == c->grid_w && G.sigma == c->grid_sigma100 / 100.0) return FPTA_OK;
@@ -40,652 +66,89 @@ int grid_build(fpta_ctx* c, Layout& L) {
   G.built = true;
   G.w = c->grid_w;
   G.sigma = c->grid_sigma100 / 100.0;
-  G.err_bound = std::exp(-M_PI * G.w * std::sqrt(1.0 - 1.0 / G.sigma));
-  if (L.segs.empty()) {
-    G.why = "gridded path: no signals";
-    return FPTA_OK;
-  }
-  for (Seg* sg : L.segs)
-    if (!sg->d.harmonic) {
-      G.why = "gridded path: every signal needs a harmonic grid f_k = k f_1";
-      return FPTA_OK;
-    }
-  // grid signals: with FPTA_OPT_GRID_COALESCE, a signal joins the first earlier grid signal with the same base
-  // frequency w0 on every pulsar and the same chromatic weight (factor x mask) on every TOA. Their sums
-  // ch(t) sum_k c_k cos(k w0 t) + s_k sin(k w0 t) then add in coefficient space (k_coef_merge): one DFT, one band.
-  {
-    const int32_t n_layout = (int32_t)L.segs.size();
-    std::vector<std::vector<double>> chv(n_layout);
-    auto ch_of = [&](int32_t i) -> const std::vector<double>& {
-      if (chv[i].empty()) {
-        const SegDesc& d = L.segs[i]->d;
-        const std::vector<uint8_t>& m = L.segs[i]->h_mask;
-        chv[i].resize(L.n_toa);
-        for (int64_t t = 0; t < L.n_toa; ++t) {
-          double ch = 1.0;  // chrom_factor (device_common.h), same operations
-          if (d.idx != 0.0) {
-            const double x = d.freqf / L.h_nu[t];
-            ch = d.idx == 2.0 ? x * x : d.idx == 1.0 ? x : std::pow(x, d.idx);
-          }
-          chv[i][t] = (!m.empty() && !m[t]) ? 0.0 : ch;
-        }
-      }
-      return chv[i];
-    };
-    auto w0_of = [&](int32_t i, int32_t p) { return L.segs[i]->h_w0[L.segs[i]->d.kind == 0 ? p : 0]; };
-    for (int32_t i = 0; i < n_layout; ++i) {
-      int32_t join = -1;
-      for (size_t g = 0; c->grid_coalesce && g < G.members.size() && join < 0; ++g) {
-        // a grid signal merges at most kGridMaxSeg other members (CoefMerge::src): a full group starts a new one
-        if (G.members[g].size() > (size_t)kGridMaxSeg) continue;
-        const int32_t f = G.members[g][0];
-        bool same = true;
-        for (int32_t p = 0; p < L.P && same; ++p) same = w0_of(i, p) == w0_of(f, p);
-        if (same) same = ch_of(i) == ch_of(f);
-        if (same) join = (int32_t)g;
-      }
-      if (join < 0) {
-        G.members.push_back({i});
-      } else {
-        G.members[join].push_back(i);
-        G.merges = true;
-      }
-    }
-    for (const std::vector<int32_t>& m : G.members) {
-      int32_t a = m[0];
-      for (int32_t i : m)
-        if (L.segs[i]->d.nm > L.segs[a]->d.nm) a = i;
-      G.anchor.push_back(a);
-      G.last.push_back(m.back());
-    }
-  }
-  const int32_t n_seg = (int32_t)G.members.size();  // grid signals from here on
-  if (n_seg > kGridMaxSeg) {
-    G.why = "gridded path: needs 1.." + std::to_string(kGridMaxSeg) + " grid signals (after coalescing)";
-    return FPTA_OK;
-  }
-  const int64_t N = L.n_toa;
-  // per (segment, TOA): first interpolation row J (unwrapped) and offset d = u - J, u = theta / h
-  std::vector<std::vector<int64_t>> J(n_seg, std::vector<int64_t>(N));
-  std::vector<std::vector<double>> D(n_seg, std::vector<double>(N));
-  std::vector<int32_t> nf(n_seg), ws(n_seg);
-  std::vector<double> betas(n_seg);
-  // Per grid signal: the options' (w, sigma) give nf0 = sigma (2 N + 1) grid points, a multiple of 4 (the MFMA DFT
-  // runs on the quarter range); it computes whole blocks of kGridDftRows rows of the quarter range, so nf1 = 4 (rows
-  // of those blocks - 1) points cost it nothing more. The larger effective oversampling sigma1 = nf1 / (2 N + 1)
-  // reaches the options' a-priori bound with a narrower kernel w1; the signal takes (nf1, w1) when its interpolation
-  // band (w + the cells a 32-TOA chunk spans) is estimated narrower.
-  const double bound_target = G.err_bound;
-  G.err_bound = 0.0;
-  for (int32_t s = 0; s < n_seg; ++s) {
-    const Seg* sg = L.segs[G.anchor[s]];
-    const SegDesc& d = sg->d;
-    int32_t n = (int32_t)std::ceil(G.sigma * (2.0 * d.nm + 1.0));
-    int32_t n0 = (std::max(n, 2 * G.w + 2) + 3) / 4 * 4, w0 = G.w;
-    // grid cells per TOA per grid point: mean over pulsars of w0 dt / (2 pi), dt the mean TOA spacing
-    double rho = 0.0;
-    for (int32_t p = 0; p < L.P; ++p) {
-      const int64_t a0 = L.h_offs[p], a1 = L.h_offs[p + 1];
-      double tmin = L.h_toas[a0], tmax = L.h_toas[a0];
-      for (int64_t t = a0; t < a1; ++t) {
-        tmin = std::min(tmin, L.h_toas[t]);
-        tmax = std::max(tmax, L.h_toas[t]);
-      }
-      if (a1 - a0 > 1) rho += sg->h_w0[d.kind == 0 ? p : 0] * (tmax - tmin) / (double)(a1 - a0 - 1) / (2.0 * M_PI);
-    }
-    rho /= L.P;
-    const int32_t blocks = (n0 / 4 + kGridDftRows) / kGridDftRows;  // ceil((nf / 4 + 1) / rows per block)
-    const int32_t n1 = 4 * (blocks * kGridDftRows - 1);
-    const double sig1 = n1 / (2.0 * d.nm + 1.0);
-    int32_t w1 = G.w;
-    while (w1 > 4 && std::exp(-M_PI * (w1 - 1) * std::sqrt(1.0 - 1.0 / sig1)) <= bound_target) --w1;
-    const bool fill = n1 > n0 && 2 * w1 + 2 <= n1 && w1 + kGridTT * n1 * rho < w0 + kGridTT * n0 * rho - 0.25;
-    nf[s] = fill ? n1 : n0;
-    ws[s] = fill ? w1 : w0;
-    const double sig = nf[s] / (2.0 * d.nm + 1.0);
-    // shape parameter of the exponential-of-semicircle kernel for oversampling sigma (2.31 w at sigma = 2)
-    betas[s] = 0.98 * M_PI * ws[s] * (1.0 - 0.5 / sig);
-    G.err_bound = std::max(G.err_bound, std::exp(-M_PI * ws[s] * std::sqrt(1.0 - 1.0 / sig)));
-    const double hw = 0.5 * ws[s];
-    const double h = 2.0 * M_PI / nf[s];
-    for (int32_t p = 0; p < L.P; ++p) {
-      const double w0 = sg->h_w0[d.kind == 0 ? p : 0];
-      for (int64_t t = L.h_offs[p]; t < L.h_offs[p + 1]; ++t) {
-        const double u = (w0 * L.h_toas[t]) / h;
-        if (!std::isfinite(u) || std::fabs(u) > 1e15) {
-          G.why = "gridded path: phase out of range";
-          return FPTA_OK;
-        }
-        const int64_t j = (int64_t)std::floor(u - hw) + 1;
-        J[s][t] = j;
-        D[s][t] = u - (double)j;
-      }
-    }
-  }
-  // chunks: <= kGridTT consecutive TOAs of one pulsar, every signal's band <= kGridRowCap rows
-  std::vector<int4> chunks;
-  std::vector<int32_t> chunk_of(N), tt_of(N);
-  std::vector<std::vector<int64_t>> band_lo(n_seg);  // per chunk: first grid row (unwrapped) of each signal
-  std::vector<std::vector<int32_t>> band_n(n_seg);   // per chunk: band rows of each signal (span + w)
-  std::vector<int64_t> lo(n_seg), hi(n_seg);
-  for (int32_t p = 0; p < L.P; ++p) {
-    int64_t t = L.h_offs[p];
-    const int64_t t_end = L.h_offs[p + 1];
-    while (t < t_end) {
-      const int64_t t0 = t;
-      for (int32_t s = 0; s < n_seg; ++s) lo[s] = hi[s] = J[s][t];
-      ++t;
-      // chunks end on multiples of kGridTT in the global TOA index: every full chunk then writes whole
-      // 256-byte runs of each realization row
-      const int64_t t_lim = std::min(t_end, (t0 / kGridTT + 1) * kGridTT);
-      while (t < t_lim) {
-        bool fits = true;
-        for (int32_t s = 0; s < n_seg && fits; ++s)
-          fits = std::max(hi[s], J[s][t]) - std::min(lo[s], J[s][t]) + ws[s] + 1 <= kGridRowCap;
-        if (!fits) break;
-        for (int32_t s = 0; s < n_seg; ++s) {
-          lo[s] = std::min(lo[s], J[s][t]);
-          hi[s] = std::max(hi[s], J[s][t]);
-        }
-        ++t;
-      }
-      const int32_t ci = (int32_t)chunks.size();
-      chunks.push_back(make_int4(p, (int)(t0 - L.h_offs[p]), (int)(t - t0), 0));
-      for (int64_t u = t0; u < t; ++u) {
-        chunk_of[u] = ci;
-        tt_of[u] = (int32_t)(u - t0);
-      }
-      for (int32_t s = 0; s < n_seg; ++s) {
-        band_lo[s].push_back(lo[s]);
-        band_n[s].push_back((int32_t)(hi[s] - lo[s]) + ws[s]);
-        for (int64_t u = t0; u < t; ++u) J[s][u] -= lo[s];  // row of the TOA's first weight in its band
-      }
-    }
-  }
-  if (chunks.size() > (size_t)0x7FFFFFFF / 8) {
-    G.why = "gridded path: too many chunks";
-    return FPTA_OK;
-  }
-  G.n_chunks = (int32_t)chunks.size();
-  G.psr_chunk0.assign((size_t)L.P + 1, 0);
-  for (int32_t ci = (int32_t)chunks.size() - 1; ci >= 0; --ci) G.psr_chunk0[chunks[ci].x] = ci;
-  G.psr_chunk0[L.P] = G.n_chunks;
-  for (int32_t p = L.P - 1; p >= 0; --p)  // a pulsar without TOAs has no chunk: it starts where the next one does
-    if (L.h_offs[p + 1] == L.h_offs[p]) G.psr_chunk0[p] = G.psr_chunk0[p + 1];
-  if (int rc0 = upload(c, G.psr_c0, G.psr_chunk0.data(), sizeof(int32_t) * G.psr_chunk0.size(), "pulsar chunks"))
-    return rc0;
-  const int32_t n_chunks = G.n_chunks;
-  // band rows of a chunk: every signal's band back to back (virtual rows voff_s ..), padded to a multiple of
-  // 4 once per chunk (k_grid_interp_mfma: 4 rows per MFMA step; pad rows re-read a valid row at weight 0), and in
-  // diagnostic builds to at least kGridMinV rows (k_grid_interp_st's operand lookahead never passes the next chunk; the
-  // product kernels would only run zero-weight steps on them)
-  std::vector<int32_t> voff((size_t)n_seg * n_chunks);
-  int32_t vmax = 4;
-  for (int32_t ci = 0; ci < n_chunks; ++ci) {
-    int32_t v = 0;
-    for (int32_t s = 0; s < n_seg; ++s) {
-      voff[(size_t)s * n_chunks + ci] = v;
-      v += band_n[s][ci];
-    }
-#ifdef FPTA_DIAG_KERNELS
-    chunks[ci].w = std::max(kGridMinV, (v + 3) & ~3);
-#else
-    chunks[ci].w = (v + 3) & ~3;
-#endif
-    vmax = std::max(vmax, chunks[ci].w);
-  }
-  if (vmax > kGridVMax) {
-    G.why = "gridded path: a chunk's band rows over all signals exceed " + std::to_string(kGridVMax);
-    return FPTA_OK;
-  }
-  G.vmax = vmax;
-  std::vector<int64_t> rowoff(n_seg);
-  int64_t grid_rows = 0;
-  for (int32_t s = 0; s < n_seg; ++s) {
-    rowoff[s] = grid_rows;
-    grid_rows += (int64_t)L.P * nf[s];
-  }
-  if (grid_rows > 0x7FFFFFFF) {
-    G.why = "gridded path: grid too large";
-    return FPTA_OK;
-  }
-  G.grid_rows = grid_rows;
-  std::vector<int32_t> rt((size_t)n_chunks * vmax);
-  for (int32_t ci = 0; ci < n_chunks; ++ci) {
-    int32_t* r = rt.data() + (size_t)ci * vmax;
-    const int32_t p = chunks[ci].x;
-    int32_t v = 0;
-    for (int32_t s = 0; s < n_seg; ++s)
-      for (int32_t i = 0; i < band_n[s][ci]; ++i) {
-        const int64_t j = ((band_lo[s][ci] + i) % nf[s] + nf[s]) % nf[s];
-        r[v++] = (int32_t)(rowoff[s] + (int64_t)p * nf[s] + j);
-      }
-    for (; v < vmax; ++v) r[v] = r[0];
-  }
-  // k_grid_interp_wr (diagnostic kernel): ring slot kWrSlots s + (unwrapped row mod kWrSlots) per band row; load
-  // lists per chunk
-  std::vector<int4> wr_meta;
-  std::vector<int2> wr_list;
-  std::vector<int32_t> wr_slot;
-#ifdef FPTA_DIAG_KERNELS
-  bool wr_ok = n_seg <= kWrMaxSig && vmax <= kWrVMax;
-#else
-  bool wr_ok = false;
-#endif
-  for (int32_t s = 0; s < n_seg && wr_ok; ++s)
-    for (int32_t ci = 0; ci < n_chunks && wr_ok; ++ci) wr_ok = band_n[s][ci] <= kWrSlots;
-  if (wr_ok) {
-    wr_meta.resize(n_chunks);
-    wr_slot.assign((size_t)n_chunks * vmax, 0);
-    for (int32_t ci = 0; ci < n_chunks; ++ci) {
-      const int32_t p = chunks[ci].x;
-      int32_t* sl = wr_slot.data() + (size_t)ci * vmax;
-      int32_t v = 0;
-      for (int32_t s = 0; s < n_seg; ++s)
-        for (int32_t i = 0; i < band_n[s][ci]; ++i)
-          sl[v++] = kWrSlots * s + (int32_t)((band_lo[s][ci] + i) & (kWrSlots - 1));
-      for (; v < vmax; ++v) sl[v] = sl[0];
-      // the bands of chunks ci - back .. ci (same pulsar) in one ring window per signal: compat (back 1) = only the rows
-      // the previous band does not hold load, after the chunk before has been computed; near (back 2) = they may load
-      // while the chunk two back is computed
-      auto window = [&](int32_t back) {
-        if (ci < back) return false;
-        for (int32_t b = 1; b <= back; ++b)
-          if (chunks[ci - b].x != p) return false;
-        for (int32_t s = 0; s < n_seg; ++s) {
-          int64_t lo = band_lo[s][ci], hi = band_lo[s][ci] + band_n[s][ci];
-          for (int32_t b = 1; b <= back; ++b) {
-            lo = std::min(lo, band_lo[s][ci - b]);
-            hi = std::max(hi, band_lo[s][ci - b] + (int64_t)band_n[s][ci - b]);
-          }
-          if (hi - lo > kWrSlots) return false;
-        }
-        return true;
-      };
-      const bool compat = window(1), near = compat && window(2);
-      auto add_rows = [&](bool only_new) {
-        int32_t n = 0;
-        for (int32_t s = 0; s < n_seg; ++s)
-          for (int32_t i = 0; i < band_n[s][ci]; ++i) {
-            const int64_t u = band_lo[s][ci] + i;
-            if (only_new && u >= band_lo[s][ci - 1] && u < band_lo[s][ci - 1] + band_n[s][ci - 1]) continue;
-            const int64_t j = (u % nf[s] + nf[s]) % nf[s];
-            wr_list.push_back(make_int2(kWrSlots * s + (int32_t)(u & (kWrSlots - 1)),
-                                        (int32_t)(rowoff[s] + (int64_t)p * nf[s] + j)));
-            ++n;
-          }
-        return n;
-      };
-      const int32_t full_off = (int32_t)wr_list.size();
-      const int32_t full_n = add_rows(false);
-      int32_t new_off = full_off, new_n = full_n;
-      if (compat) {
-        new_off = (int32_t)wr_list.size();
-        new_n = add_rows(true);
-      }
-      wr_meta[ci] = make_int4(full_off, full_n, new_off, new_n | (compat ? 0 : kWrFresh) | (near ? 0 : kWrFar));
-    }
-  }
-  // LDS-staged interpolation (k_grid_interp_lds): groups of <= kLdsGroup consecutive chunks of one pulsar whose
-  // bands, over all signals, unite to <= kLdsRowsMax rows. Per group the union's grid-buffer rows (signal by
-  // signal, each signal's rows one contiguous unwrapped range), per chunk the union slot of each band row.
-  std::vector<int4> groups;
-  std::vector<int32_t> urows, lrt((size_t)n_chunks * vmax);
-  int32_t umax = 0;
-  bool lds_ok = true;
-  for (int32_t ci = 0; ci < n_chunks && lds_ok;) {
-    const int32_t p = chunks[ci].x;
-    auto union_rows = [&](int32_t n) {
-      int64_t u = 0;
-      for (int32_t s = 0; s < n_seg; ++s) {
-        int64_t lo = band_lo[s][ci], end = band_lo[s][ci] + band_n[s][ci];
-        for (int32_t k = 1; k < n; ++k) {
-          lo = std::min(lo, band_lo[s][ci + k]);
-          end = std::max(end, band_lo[s][ci + k] + (int64_t)band_n[s][ci + k]);
-        }
-        u += end - lo;
-      }
-      return u;
-    };
-    int32_t n = 1;
-    while (n < kLdsGroup && ci + n < n_chunks && chunks[ci + n].x == p && union_rows(n + 1) <= kLdsRowsMax) ++n;
-    const int64_t U = union_rows(n);
-    if (U > kLdsRowsMax) {
-      lds_ok = false;  // one chunk's bands alone exceed the LDS budget: the register-tiled kernel serves the layout
-      break;
-    }
-    groups.push_back(make_int4(ci, n, (int32_t)U, (int32_t)urows.size()));
-    umax = std::max(umax, (int32_t)U);
-    int32_t uoff = 0;
-    for (int32_t s = 0; s < n_seg; ++s) {
-      int64_t lo = band_lo[s][ci], end = band_lo[s][ci] + band_n[s][ci];
-      for (int32_t k = 1; k < n; ++k) {
-        lo = std::min(lo, band_lo[s][ci + k]);
-        end = std::max(end, band_lo[s][ci + k] + (int64_t)band_n[s][ci + k]);
-      }
-      for (int64_t j = lo; j < end; ++j)
-        urows.push_back((int32_t)(rowoff[s] + (int64_t)p * nf[s] + ((j % nf[s]) + nf[s]) % nf[s]));
-      for (int32_t k = 0; k < n; ++k) {  // chunk ci + k: signal s's band rows start at slot uoff + (its lo - lo)
-        int32_t v = 0;
-        for (int32_t s2 = 0; s2 < s; ++s2) v += band_n[s2][ci + k];
-        for (int32_t i = 0; i < band_n[s][ci + k]; ++i)
-          lrt[(size_t)(ci + k) * vmax + v + i] = uoff + (int32_t)(band_lo[s][ci + k] - lo) + i;
-      }
-      uoff += (int32_t)(end - lo);
-    }
-    for (int32_t k = 0; k < n; ++k) {  // pad rows: any valid slot (weight 0)
-      int32_t* r = lrt.data() + (size_t)(ci + k) * vmax;
-      int32_t v = 0;
-      for (int32_t s = 0; s < n_seg; ++s) v += band_n[s][ci + k];
-      for (; v < vmax; ++v) r[v] = r[0];
-    }
-    ci += n;
-  }
-  G.lds_ok = lds_ok && !groups.empty();
-  G.n_groups = (int32_t)groups.size();
-  G.lds_rows = umax;
-  // k_grid_interp_u plan (diagnostic builds): the same grouping under the tighter LDS budget of two workgroups per CU
-  std::vector<int4> ug;
-  std::vector<int32_t> uur, ucb, uwr;
-#ifdef FPTA_DIAG_KERNELS
-  bool u_ok = n_seg <= kUnionSigMax;
-#else
-  bool u_ok = false;
-#endif
-  for (int32_t ci = 0; ci < n_chunks && u_ok;) {
-    const int32_t p = chunks[ci].x;
-    auto span = [&](int32_t s, int32_t n, int64_t& lo, int64_t& end) {
-      lo = band_lo[s][ci];
-      end = band_lo[s][ci] + band_n[s][ci];
-      for (int32_t k = 1; k < n; ++k) {
-        lo = std::min(lo, band_lo[s][ci + k]);
-        end = std::max(end, band_lo[s][ci + k] + (int64_t)band_n[s][ci + k]);
-      }
-    };
-    auto union_rows = [&](int32_t n) {
-      int64_t u = 0, lo, end;
-      for (int32_t s = 0; s < n_seg; ++s) {
-        span(s, n, lo, end);
-        u += end - lo;
-      }
-      return u;
-    };
-    int32_t n = 1;
-    while (n < kUnionGroup && ci + n < n_chunks && chunks[ci + n].x == p && union_rows(n + 1) <= kUnionRowsMax) ++n;
-    const int64_t U = union_rows(n);
-    if (U > kUnionRowsMax) {
-      u_ok = false;
-      break;
-    }
-    ug.push_back(make_int4(ci, n, (int32_t)U, (int32_t)uur.size()));
-    int32_t uoff = 0;
-    std::vector<int32_t> cb((size_t)n * 2 * kUnionSigMax, 0);
-    for (int32_t s = 0; s < n_seg; ++s) {
-      int64_t lo, end;
-      span(s, n, lo, end);
-      for (int64_t j = lo; j < end; ++j)
-        uur.push_back((int32_t)(rowoff[s] + (int64_t)p * nf[s] + ((j % nf[s]) + nf[s]) % nf[s]));
-      for (int32_t k = 0; k < n; ++k) {
-        const int32_t vo = voff[(size_t)s * n_chunks + ci + k];
-        cb[(size_t)k * 2 * kUnionSigMax + s] = vo;
-        cb[(size_t)k * 2 * kUnionSigMax + kUnionSigMax + s] = uoff + (int32_t)(band_lo[s][ci + k] - lo) - vo;
-      }
-      uoff += (int32_t)(end - lo);
-    }
-    for (int32_t k = 0; k < n; ++k)
-      for (int32_t s = n_seg; s < kUnionSigMax; ++s) {  // absent signals: never selected (offset past every row)
-        cb[(size_t)k * 2 * kUnionSigMax + s] = 1 << 20;
-        cb[(size_t)k * 2 * kUnionSigMax + kUnionSigMax + s] = 0;
-      }
-    ucb.insert(ucb.end(), cb.begin(), cb.end());
-    ci += n;
-  }
-  G.u_ok = u_ok && !ug.empty();
-  G.u_groups = (int32_t)ug.size();
-  G.u_sig = n_seg;
-  if (G.u_ok) {
-    uwr.assign((size_t)n_chunks * n_seg * kGridTT, -(1 << 20));  // empty TOA slots: every weight 0
-    for (int32_t s = 0; s < n_seg; ++s)
-      for (int64_t t = 0; t < N; ++t)
-        uwr[((size_t)chunk_of[t] * n_seg + s) * kGridTT + tt_of[t]] =
-            (int32_t)J[s][t] + voff[(size_t)s * n_chunks + chunk_of[t]];
-    for (int32_t s = 0; s < n_seg; ++s) {
-      G.u_w[s] = ws[s];
-      G.u_hw[s] = 0.5 * (double)ws[s];
-      G.u_beta[s] = betas[s];
-    }
-  }
+  PlanLayout V;
+  V.P = L.P;
+  V.n_toa = L.n_toa;
+  V.offs = L.h_offs.data();
+  V.toas = L.h_toas.data();
+  V.nu = L.h_nu.data();
+  for (const Seg* sg : L.segs)
+    V.sigs.push_back(PlanSignal{sg->d.kind, sg->d.nm, sg->d.idx, sg->d.freqf, sg->d.harmonic, sg->h_w0.data(),
+                                sg->h_mask.empty() ? nullptr : sg->h_mask.data()});
+  HostGridPlan H = plan_grid(V, PlanOptions{G.w, G.sigma, c->grid_coalesce != 0, c->grid_mfma});
+  static_cast<PlanFigures&>(G) = H;  // a refused plan keeps what the stages before the refusal made
+  G.ok = false;                       // until the tables are on the device
+  if (!G.fused_ok) G.fused_lds = 0;   // the planner reports the bytes that were too many
   int rc;
-  G.wr_ok = wr_ok;
-  if (wr_ok && ((rc = upload(c, G.wr_meta, wr_meta.data(), sizeof(int4) * wr_meta.size(), "window plan")) ||
-                (rc = upload(c, G.wr_list, wr_list.data(), sizeof(int2) * std::max<size_t>(wr_list.size(), 1),
-                             "window rows")) ||
-                (rc = upload(c, G.wr_slot, wr_slot.data(), sizeof(int32_t) * wr_slot.size(), "window slots"))))
-    return rc;
-  if ((rc = upload(c, G.chunks, chunks.data(), sizeof(int4) * chunks.size(), "grid chunks")) ||
-      (rc = upload(c, G.rows, rt.data(), sizeof(int32_t) * rt.size(), "grid band rows")))
-    return rc;
-  if (G.lds_ok && ((rc = upload(c, G.groups, groups.data(), sizeof(int4) * groups.size(), "grid groups")) ||
-                   (rc = upload(c, G.urows, urows.data(), sizeof(int32_t) * urows.size(), "grid union rows")) ||
-                   (rc = upload(c, G.lrows, lrt.data(), sizeof(int32_t) * lrt.size(), "grid LDS rows"))))
-    return rc;
-  if (G.u_ok) {
-    if ((rc = upload(c, G.ugroups, ug.data(), sizeof(int4) * ug.size(), "union groups")) ||
-        (rc = upload(c, G.uurows, uur.data(), sizeof(int32_t) * uur.size(), "union rows")) ||
-        (rc = upload(c, G.ucbase, ucb.data(), sizeof(int32_t) * ucb.size(), "union bases")) ||
-        (rc = upload(c, G.uwrow, uwr.data(), sizeof(int32_t) * uwr.size(), "union window rows")))
+  if (!H.psr_chunk0.empty()) {  // the chunks were made
+    G.n_chunks = H.n_chunks();
+    if ((rc = upload(c, G.psr_c0, G.psr_chunk0.data(), sizeof(int32_t) * G.psr_chunk0.size(), "pulsar chunks")))
       return rc;
-    const size_t dbytes = sizeof(double) * 2 * (size_t)n_chunks * n_seg * kGridTT;
-    HIPCHK(c, G.udch.ensure(dbytes), "union weight parameters alloc");
-    HIPCHK(c, hipMemsetAsync(G.udch.p, 0, dbytes, c->stream), "union weight parameters memset");
   }
-  DevBuf d_chunk_of, d_tt_of, d_row, d_d;
-  if ((rc = upload(c, d_chunk_of, chunk_of.data(), sizeof(int32_t) * N, "grid chunk_of")) ||
-      (rc = upload(c, d_tt_of, tt_of.data(), sizeof(int32_t) * N, "grid tt_of")))
+  if (!H.ok) return FPTA_OK;
+  const int32_t n_seg = H.n_seg();
+  const int64_t N = L.n_toa;
+  if ((rc = upload(c, G.chunks, H.chunks.data(), sizeof(int4) * H.chunks.size(), "grid chunks")) ||
+      (rc = upload(c, G.rows, H.rows.data(), sizeof(int32_t) * H.rows.size(), "grid band rows")))
     return rc;
-  // + kFusedPadRows band rows after the last chunk: k_grid_fused loads NQ band steps' weights of every chunk unclamped
-  const size_t wbytes = sizeof(double) * ((size_t)n_chunks * vmax + kFusedPadRows) * kGridTT;
+#ifdef FPTA_DIAG_KERNELS
+  if ((rc = grid_build_diag(c, G.diag, H))) return rc;
+#endif
+  DevBuf d_chunk_of, d_tt_of, d_row, d_d;
+  if ((rc = upload(c, d_chunk_of, H.chunk_of.data(), sizeof(int32_t) * N, "grid chunk_of")) ||
+      (rc = upload(c, d_tt_of, H.tt_of.data(), sizeof(int32_t) * N, "grid tt_of")))
+    return rc;
+  const size_t wbytes = sizeof(double) * H.wd_size;
   HIPCHK(c, G.wd.ensure(wbytes), "grid weights alloc");
   HIPCHK(c, hipMemsetAsync(G.wd.p, 0, wbytes, c->stream), "grid weights memset");
-  std::vector<double> gx, gw;
-  gauss_legendre(256, gx, gw);
-  G.fma_direct = 0.0;
-  G.fma_grid = 0.0;
-  G.fma_interp = 0.0;
-  G.fma_dft = 0.0;
-  G.grid_vals = 0.0;
-  for (int32_t ci = 0; ci < n_chunks; ++ci) G.fma_interp += (double)chunks[ci].w * kGridTT;
-  G.mean_v = G.fma_interp / kGridTT / std::max(n_chunks, 1);
-  G.weight_bytes = (double)wbytes;
-  for (Seg* sg : L.segs) G.fma_direct += 2.0 * sg->d.nm * (double)N;
-  for (int32_t s = 0; s < n_seg; ++s) {
-    const SegDesc& d = L.segs[G.anchor[s]]->d;
-    GridSeg* gs = new GridSeg();
-    G.segs.push_back(gs);
-    gs->nf = nf[s];
-    gs->half = nf[s] / 2;
-    gs->lde = (gs->half + kGridDftRows) / kGridDftRows * kGridDftRows;  // row blocks of k_grid_dft_mfma and k_grid_dft
-    gs->ntab = (d.nm + 7) / 8 * 8;         // whole pairs of 4-mode MFMA k-steps (zero rows)
-    gs->rowoff = rowoff[s];
-    // q_k = (2 pi / nf) / phi_hat(k), phi_hat(k) = alpha int_{-1}^{1} phi(z) cos(k alpha z) dz, alpha = pi w / nf
-    const double alpha = M_PI * ws[s] / nf[s], beta = betas[s];
-    std::vector<double> ec((size_t)gs->ntab * gs->lde, 0.0), es((size_t)gs->ntab * gs->lde, 0.0);
-    for (int32_t m = 0; m < d.nm; ++m) {
-      const int64_t k = m + 1;
-      double ph = 0.0;
-      for (size_t q = 0; q < gx.size(); ++q)
-        ph += gw[q] * std::exp(beta * (std::sqrt(1.0 - gx[q] * gx[q]) - 1.0)) * std::cos(k * alpha * gx[q]);
-      const double qk = (2.0 * M_PI / nf[s]) / (alpha * ph);
-      for (int32_t j = 0; j <= gs->half; ++j) {
-        const double a = 2.0 * M_PI * (double)((k * j) % nf[s]) / nf[s];  // exact argument reduction
-        ec[(size_t)m * gs->lde + j] = qk * std::cos(a);
-        es[(size_t)m * gs->lde + j] = qk * std::sin(a);
-      }
-    }
-    if ((rc = upload(c, gs->ecos, ec.data(), sizeof(double) * ec.size(), "grid ecos")) ||
-        (rc = upload(c, gs->esin, es.data(), sizeof(double) * es.size(), "grid esin")))
-      return rc;
-    // quarter-range tables by parity: [0] cos / [1] sin of odd k = 2 t + 1 (m = 2 t), [2] / [3] of even k = 2 t + 2
-    gs->ldq = (nf[s] / 4 + kGridDftRows) / kGridDftRows * kGridDftRows;
-    gs->ntq = ((d.nm + 1) / 2 + 7) / 8 * 8;
-    std::vector<double> tq((size_t)4 * gs->ntq * gs->ldq, 0.0);
-    for (int32_t m = 0; m < d.nm; ++m) {
-      const int32_t par = m & 1, t = m >> 1;
-      for (int32_t j = 0; j <= nf[s] / 4; ++j) {
-        tq[((size_t)(2 * par) * gs->ntq + t) * gs->ldq + j] = ec[(size_t)m * gs->lde + j];
-        tq[((size_t)(2 * par + 1) * gs->ntq + t) * gs->ldq + j] = es[(size_t)m * gs->lde + j];
-      }
-    }
-    if ((rc = upload(c, gs->tq, tq.data(), sizeof(double) * tq.size(), "grid quarter tables"))) return rc;
-    // weight rows of signal s: its band's virtual offset in the chunk + the TOA's first row in the band
-    std::vector<int32_t> row(N);
-    for (int64_t t = 0; t < N; ++t) row[t] = (int32_t)J[s][t] + voff[(size_t)s * n_chunks + chunk_of[t]];
-    if ((rc = upload(c, d_row, row.data(), sizeof(int32_t) * N, "grid rows")) ||
-        (rc = upload(c, d_d, D[s].data(), sizeof(double) * N, "grid offsets")))
+  // per grid signal its tables, then its weights; half: into the half-chunk bands' layout
+  auto weights = [&](int32_t s, bool half) -> int {
+    const PlanSeg& g = H.segs[s];
+    const std::vector<int32_t>& row = half ? g.hrow_of : g.row;
+    if ((rc = upload(c, d_row, row.data(), sizeof(int32_t) * N, half ? "half rows" : "grid rows")) ||
+        (rc = upload(c, d_d, g.d.data(), sizeof(double) * N, "grid offsets")))
       return rc;
     HIPCHK(c,
-           launch_grid_weights(c->stream, d, N, L.nu.as<double>(), d_chunk_of.as<int32_t>(), d_tt_of.as<int32_t>(),
-                               d_row.as<int32_t>(), d_d.as<double>(), ws[s], beta, vmax, G.wd.as<double>(),
-                               G.u_ok ? G.udch.as<double>() : nullptr, s, n_seg),
-           "k_grid_weights launch");
-    HIPCHK(c, hipStreamSynchronize(c->stream), "grid weights sync");  // d_row / d_d are reused
-    // multiply-adds per realization: quarter range by parity on MFMA, half range on VALU
-    G.fma_dft += (double)L.P * ((c->grid_mfma & 1) ? (gs->nf / 4 + 1) * 2.0 * d.nm : (gs->half + 1) * 2.0 * d.nm);
-    G.grid_vals += (double)L.P * gs->nf;
-    G.fma_grid = G.fma_dft + G.fma_interp;
+           launch_grid_weights(c->stream, L.segs[G.anchor[s]]->d, N, L.nu.as<double>(), d_chunk_of.as<int32_t>(),
+                               d_tt_of.as<int32_t>(), d_row.as<int32_t>(), d_d.as<double>(), g.w, g.beta,
+                               half ? H.fused_hvmax : H.vmax, half ? G.hwd.as<double>() : G.wd.as<double>(),
+                               !half && G.diag.u_ok ? G.diag.udch.as<double>() : nullptr, s, n_seg, half ? 1 : 0),
+           half ? "k_grid_weights (half bands) launch" : "k_grid_weights launch");
+    // d_row / d_d are reused
+    HIPCHK(c, hipStreamSynchronize(c->stream), half ? "half weights sync" : "grid weights sync");
+    return FPTA_OK;
+  };
+  for (int32_t s = 0; s < n_seg; ++s) {
+    const PlanSeg& g = H.segs[s];
+    GridSeg* gs = new GridSeg();
+    G.segs.push_back(gs);
+    gs->nf = g.nf;
+    gs->half = g.half;
+    gs->lde = g.lde;
+    gs->ntab = g.ntab;
+    gs->rowoff = g.rowoff;
+    gs->ldq = g.ldq;
+    gs->ntq = g.ntq;
+    if ((rc = upload(c, gs->ecos, g.ecos.data(), sizeof(double) * g.ecos.size(), "grid ecos")) ||
+        (rc = upload(c, gs->esin, g.esin.data(), sizeof(double) * g.esin.size(), "grid esin")) ||
+        (rc = upload(c, gs->tq, g.tq.data(), sizeof(double) * g.tq.size(), "grid quarter tables")) ||
+        (rc = weights(s, false)))
+      return rc;
   }
-  // k_grid_fused: the grids of kFusedReal realizations plus the draw ring fit in LDS, n_seg <= kFusedMaxSig, and every
-  // 32-row DFT chunk is one DFT wave's job
-  {
-    int32_t jobs = 0, rows = 0;
-    bool ok = n_seg <= kFusedMaxSig;
-    for (int32_t s = 0; s < n_seg && ok; ++s) {
-      const GridSeg* gs = G.segs[s];
-      ok = gs->nf % 4 == 0 && gs->ldq == (gs->nf / 4 + 32) / 32 * 32;
-      G.fused_lrow0.push_back(rows);
-      jobs += (gs->nf / 4 + 32) / 32;
-      rows += gs->nf;
-    }
-    const size_t lds = sizeof(double) * ((size_t)rows * kFusedPitch + 2 * kFusedMaxSig * kFusedSlot) + 48;
-    bool members_ok = true;
-    for (const std::vector<int32_t>& m : G.members) members_ok = members_ok && m.size() <= (size_t)kDftGenTerms;
-    ok = ok && members_ok && jobs <= kFusedDW && lds <= (size_t)kFusedLdsMax;
-    if (ok) {
-      // [n_chunks][4][fq]: band row 4 q + j of a chunk at [j][q] (a lane's rows of consecutive steps contiguous: 16-byte
-      // loads), fq = the band steps rounded up to 4 and at least kFusedFqMin; steps past the chunk's repeat its first row
-      const int32_t fq = std::max(kFusedFqMin, (vmax / 4 + 3) & ~3);
-      std::vector<int32_t> band_row(vmax);
-      std::vector<int32_t> lrt((size_t)n_chunks * 4 * fq);
-      for (int32_t ci = 0; ci < n_chunks; ++ci) {
-        int32_t v = 0;
-        for (int32_t s = 0; s < n_seg; ++s)
-          for (int32_t i = 0; i < band_n[s][ci]; ++i)
-            band_row[v++] = G.fused_lrow0[s] + (int32_t)(((band_lo[s][ci] + i) % nf[s] + nf[s]) % nf[s]);
-        for (; v < vmax; ++v) band_row[v] = band_row[0];
-        int32_t* r = lrt.data() + (size_t)ci * 4 * fq;
-        for (int32_t j = 0; j < 4; ++j)
-          for (int32_t q = 0; q < fq; ++q) r[j * fq + q] = 4 * q + j < vmax ? band_row[4 * q + j] : band_row[0];
-      }
-      if ((rc = upload(c, G.frows, lrt.data(), sizeof(int32_t) * lrt.size(), "fused LDS rows"))) return rc;
-      G.fused_fq = fq;
-      G.fused_lds = lds;
-    }
-    G.fused_ok = ok;
-    // Half-chunk bands (FusedHalf): TOAs 0..15 and 16..31 of each chunk get bands of their own (a 32-TOA chunk's band
-    // is w + the cells its 32 TOAs span; a half's, w + the cells of 16). Per half the signals' bands back to back,
-    // padded to whole band steps; the weights by the half-band layout of k_grid_weights.
-    if (ok) {
-      std::vector<int4> hch(n_chunks);
-      std::vector<int32_t> hv((size_t)2 * n_chunks, 0);                    // band rows of each half (padded)
-      std::vector<int32_t> hrow_of(N), hchunk_of(N), htt_of(N);            // per TOA (filled per signal below)
-      std::vector<std::vector<int64_t>> hlo(n_seg, std::vector<int64_t>((size_t)2 * n_chunks, 0));
-      std::vector<std::vector<int32_t>> hvoff(n_seg, std::vector<int32_t>((size_t)2 * n_chunks, 0));
-      std::vector<std::vector<int32_t>> hn(n_seg, std::vector<int32_t>((size_t)2 * n_chunks, 0));
-      double steps_full = 0.0, steps_half = 0.0;
-      for (int32_t ci = 0; ci < n_chunks; ++ci) {
-        const int64_t a0 = L.h_offs[chunks[ci].x] + chunks[ci].y, a1 = a0 + chunks[ci].z;
-        int32_t nqh[2] = {0, 0};
-        for (int32_t h = 0; h < 2; ++h) {
-          const int64_t b0 = a0 + kFusedHalfTT * h, b1 = std::min(a1, b0 + kFusedHalfTT);
-          if (b0 >= b1) continue;
-          int32_t v = 0;
-          for (int32_t s = 0; s < n_seg; ++s) {
-            int64_t lo1 = INT64_MAX, hi1 = INT64_MIN;
-            for (int64_t u = b0; u < b1; ++u) {
-              const int64_t j = J[s][u] + band_lo[s][ci];  // unwrapped first row of the TOA
-              lo1 = std::min(lo1, j);
-              hi1 = std::max(hi1, j);
-            }
-            const size_t hc = (size_t)2 * ci + h;
-            hlo[s][hc] = lo1;
-            hvoff[s][hc] = v;
-            hn[s][hc] = (int32_t)(hi1 - lo1) + ws[s];
-            v += hn[s][hc];
-          }
-          hv[(size_t)2 * ci + h] = (v + 3) & ~3;
-          nqh[h] = hv[(size_t)2 * ci + h] / 4;
-          for (int64_t u = b0; u < b1; ++u) {
-            hchunk_of[u] = 2 * ci + h;
-            htt_of[u] = (int32_t)(u - b0);
-          }
-        }
-        hch[ci] = make_int4(chunks[ci].x, chunks[ci].y, chunks[ci].z, nqh[0] | (nqh[1] << 16));
-        steps_full += 4.0 * (chunks[ci].w / 4);
-        steps_half += 4.0 * std::max(nqh[0], nqh[1]);  // the kernel runs both halves' longer step count
-      }
-      int32_t hvmax = 8;
-      for (int32_t v : hv) hvmax = std::max(hvmax, (v + 7) & ~7);
-      const int32_t hfq = std::max(kFusedHalfNQ, (hvmax / 4 + 3) & ~3);
-      std::vector<int32_t> hrt((size_t)n_chunks * 2 * 4 * hfq);
-      for (int32_t ci = 0; ci < n_chunks; ++ci)
-        for (int32_t h = 0; h < 2; ++h) {
-          const size_t hc = (size_t)2 * ci + h;
-          std::vector<int32_t> band_row(std::max(hv[hc], 1), G.fused_lrow0[0]);
-          int32_t v = 0;
-          for (int32_t s = 0; s < n_seg; ++s)
-            for (int32_t i = 0; i < hn[s][hc]; ++i)
-              band_row[v++] = G.fused_lrow0[s] + (int32_t)(((hlo[s][hc] + i) % nf[s] + nf[s]) % nf[s]);
-          for (; v < (int32_t)band_row.size(); ++v) band_row[v] = band_row[0];
-          int32_t* r = hrt.data() + hc * 4 * hfq;
-          for (int32_t j = 0; j < 4; ++j)
-            for (int32_t q = 0; q < hfq; ++q)
-              r[j * hfq + q] = 4 * q + j < hv[hc] ? band_row[4 * q + j] : band_row[0];
-        }
-      if ((rc = upload(c, G.hchunks, hch.data(), sizeof(int4) * hch.size(), "fused half chunks")) ||
-          (rc = upload(c, G.hrows, hrt.data(), sizeof(int32_t) * hrt.size(), "fused half rows")))
-        return rc;
-      // + the rows the kernel's unconditional loads may read past the last half (kFusedHalfNQ steps)
-      const size_t hbytes = sizeof(double) * ((size_t)2 * n_chunks * hvmax + 4 * kFusedHalfNQ) * kFusedHalfTT;
-      HIPCHK(c, G.hwd.ensure(hbytes), "half weights alloc");
-      HIPCHK(c, hipMemsetAsync(G.hwd.p, 0, hbytes, c->stream), "half weights memset");
-      if ((rc = upload(c, d_chunk_of, hchunk_of.data(), sizeof(int32_t) * N, "half chunk_of")) ||
-          (rc = upload(c, d_tt_of, htt_of.data(), sizeof(int32_t) * N, "half tt_of")))
-        return rc;
-      for (int32_t s = 0; s < n_seg; ++s) {
-        const SegDesc& d = L.segs[G.anchor[s]]->d;
-        for (int64_t t = 0; t < N; ++t) {
-          const size_t hc = (size_t)hchunk_of[t];
-          hrow_of[t] = (int32_t)(J[s][t] + band_lo[s][hc / 2] - hlo[s][hc]) + hvoff[s][hc];
-        }
-        if ((rc = upload(c, d_row, hrow_of.data(), sizeof(int32_t) * N, "half rows")) ||
-            (rc = upload(c, d_d, D[s].data(), sizeof(double) * N, "grid offsets")))
-          return rc;
-        HIPCHK(c,
-               launch_grid_weights(c->stream, d, N, L.nu.as<double>(), d_chunk_of.as<int32_t>(), d_tt_of.as<int32_t>(),
-                                   d_row.as<int32_t>(), d_d.as<double>(), ws[s], betas[s], hvmax, G.hwd.as<double>(),
-                                   nullptr, s, n_seg, 1),
-               "k_grid_weights (half bands) launch");
-        HIPCHK(c, hipStreamSynchronize(c->stream), "half weights sync");  // d_row / d_d are reused
-      }
-      int32_t hnq = 1;
-      for (int32_t v : hv) hnq = std::max(hnq, v / 4);
-      G.fused_hfq = hfq;
-      G.fused_hvmax = hvmax;
-      G.fused_hnq = hnq;
-      G.fused_half_gain = steps_half > 0.0 ? steps_full / steps_half : 0.0;
-      G.fma_interp_half = steps_half * 4.0 * kGridTT / 4.0;  // 4 rows x 32 TOAs per (both-halves) step
-      G.fused_half_ok = true;
-    }
+  if (H.fused_ok && (rc = upload(c, G.frows, H.frows.data(), sizeof(int32_t) * H.frows.size(), "fused LDS rows")))
+    return rc;
+  if (H.fused_half_ok) {
+    if ((rc = upload(c, G.hchunks, H.hchunks.data(), sizeof(int4) * H.hchunks.size(), "fused half chunks")) ||
+        (rc = upload(c, G.hrows, H.hrows.data(), sizeof(int32_t) * H.hrows.size(), "fused half rows")))
+      return rc;
+    const size_t hbytes = sizeof(double) * H.hwd_size;
+    HIPCHK(c, G.hwd.ensure(hbytes), "half weights alloc");
+    HIPCHK(c, hipMemsetAsync(G.hwd.p, 0, hbytes, c->stream), "half weights memset");
+    if ((rc = upload(c, d_chunk_of, H.hchunk_of.data(), sizeof(int32_t) * N, "half chunk_of")) ||
+        (rc = upload(c, d_tt_of, H.htt_of.data(), sizeof(int32_t) * N, "half tt_of")))
+      return rc;
+    for (int32_t s = 0; s < n_seg; ++s)
+      if ((rc = weights(s, true))) return rc;
   }
   G.ok = true;
   return FPTA_OK;
@@ -924,23 +387,24 @@ int grid_run(fpta_ctx* c, Layout& L, SynthArgs& a, int32_t R_pad, bool pipe) {
   int kind;  // the interpolation kernel (fpta_batch_grid_info_n slot 15)
   if (false) {
 #ifdef FPTA_DIAG_KERNELS
-  } else if (c->interp_ws == 5 && !c->interp_lds && G.u_ok && !a.w_on) {
+  } else if (c->interp_ws == 5 && !c->interp_lds && G.diag.u_ok && !a.w_on) {
     kind = 5;
     band.pgfirst = nullptr;  // the diagnostic kernels write one partial row per chunk
     band.n_pg = G.n_chunks;
-    GridUnion un{G.ugroups.as<int4>(), G.uurows.as<int32_t>(), G.ucbase.as<int32_t>(), G.udch.as<double>(),
-                 G.uwrow.as<int32_t>(), G.u_groups, G.u_sig, {G.u_w[0], G.u_w[1]}, {G.u_hw[0], G.u_hw[1]},
-                 {G.u_beta[0], G.u_beta[1]}};
+    const GridPlan::Diag& D = G.diag;
+    GridUnion un{D.ugroups.as<int4>(), D.uurows.as<int32_t>(), D.ucbase.as<int32_t>(), D.udch.as<double>(),
+                 D.uwrow.as<int32_t>(), D.u_groups, D.u_sig, {D.u_w[0], D.u_w[1]}, {D.u_hw[0], D.u_hw[1]},
+                 {D.u_beta[0], D.u_beta[1]}};
     HIPCHK(c, launch_grid_interp_u(c->stream, a, band, un, R_pad), "k_grid_interp_u launch");
   } else if (c->interp_ws == 4 && !c->interp_lds) {
     kind = 4;
     band.pgfirst = nullptr;
     band.n_pg = G.n_chunks;
     HIPCHK(c, launch_grid_interp_st(c->stream, a, band, R_pad), "k_grid_interp_st launch");
-  } else if (c->interp_wr && G.wr_ok && !c->interp_lds && c->interp_ws > 0 && !a.w_on && !a.accumulate && !a.part &&
-             R_pad % kWrReal == 0 && !psr) {
+  } else if (c->interp_wr && G.diag.wr_ok && !c->interp_lds && c->interp_ws > 0 && !a.w_on && !a.accumulate &&
+             !a.part && R_pad % kWrReal == 0 && !psr) {
     kind = 10;
-    GridWindow wrp{G.wr_meta.as<int4>(), G.wr_list.as<int2>(), G.wr_slot.as<int32_t>()};
+    GridWindow wrp{G.diag.wr_meta.as<int4>(), G.diag.wr_list.as<int2>(), G.diag.wr_slot.as<int32_t>()};
     HIPCHK(c, launch_grid_interp_wr(c->stream, a, band, wrp, R_pad), "k_grid_interp_wr launch");
 #endif
   } else if (fused) {
@@ -1102,11 +566,12 @@ int grid_run(fpta_ctx* c, Layout& L, SynthArgs& a, int32_t R_pad, bool pipe) {
     kind = 1;
     HIPCHK(c, launch_grid_interp_ws(c->stream, a, band, R_pad), "k_grid_interp_ws launch");
 #ifdef FPTA_DIAG_KERNELS
-  } else if (c->interp_lds && G.lds_ok && !a.w_on) {
+  } else if (c->interp_lds && G.diag.lds_ok && !a.w_on) {
     kind = 3;
     band.pgfirst = nullptr;
     band.n_pg = G.n_chunks;
-    GridLds lds{G.groups.as<int4>(), G.urows.as<int32_t>(), G.lrows.as<int32_t>(), G.n_groups, G.lds_rows};
+    const GridPlan::Diag& D = G.diag;
+    GridLds lds{D.groups.as<int4>(), D.urows.as<int32_t>(), D.lrows.as<int32_t>(), D.n_groups, D.lds_rows};
     HIPCHK(c, launch_grid_interp_lds(c->stream, a, band, lds, R_pad), "k_grid_interp_lds launch");
 #endif
   } else {
