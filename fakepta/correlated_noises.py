@@ -6,12 +6,12 @@ vector), computes the same SVD square root of the ORF that numpy's multivariate_
 uses, and hands the draws to the GPU, which applies the ORF factor and evaluates every
 pulsar's Fourier sum (libfakepta_amd: fpta_common_accumulate).
 """
-import importlib
 import inspect
 
 import numpy as np
 
 from fakepta_amd import _capi
+from fakepta_amd import orf as _orf
 from . import spectrum as _spectrum_module
 from .fake_pta import Pulsar  # noqa: F401  (reference module namespace)
 from .fake_pta import reconstruct_array
@@ -78,19 +78,19 @@ def hd(psrs):
 
 
 def anisotropic(psrs, h_map):
-    """ORF of an anisotropic GWB given as a healpy map (correlated_noises.py:73-89). Needs healpy."""
-    hp = importlib.import_module('healpy')
-    npix = len(h_map)
-    gwtheta, gwphi = hp.pix2ang(hp.npix2nside(npix), np.arange(npix), nest=False)
-    fp, fc = [], []
-    for psr in psrs:
-        a, b, _ = create_gw_antenna_pattern(psr.pos, gwtheta, gwphi)
-        fp.append(a)
-        fc.append(b)
-    fp, fc = np.array(fp), np.array(fc)
-    orf = 1.5 * ((fp * h_map) @ fp.T + (fc * h_map) @ fc.T) / npix
-    orf[np.diag_indices_from(orf)] *= 2.0
-    return orf
+    """ORF of an anisotropic GWB given as a HEALPix RING map (correlated_noises.py:73-89): the pixel centres and the
+    antenna-pattern Gram matrix are native (fpta_orf_anisotropic), no healpy. A pulsar exactly on a pixel centre
+    gives a NaN row and column, as in the reference (D14)."""
+    return _orf.anisotropic_orf(_positions(psrs), np.asarray(h_map, dtype=float).ravel())
+
+
+def anisotropic_array(psrs, h_maps):
+    """One ORF per map, [M, P, P], for maps [M, npix] from one GPU call: the maps share the antenna patterns (e.g. the
+    maps of a spherical-harmonic basis)."""
+    h_maps = np.asarray(h_maps, dtype=float)
+    if h_maps.ndim != 2:
+        raise ValueError('anisotropic_array: h_maps must be [M, npix]')
+    return _orf.anisotropic_orf(_positions(psrs), h_maps)
 
 
 def monopole(psrs):

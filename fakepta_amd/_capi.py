@@ -42,6 +42,9 @@ _SIGS = [
     ("fpta_ephem_kepler", _c_int, [_ctx_p, _i64, _vp, _vp, _vp]),
     ("fpta_ephem_orbits", _c_int, [_ctx_p, _i64, _vp, _i32, _vp, _vp, _vp]),
     ("fpta_roemer_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _dbl, _i32, _vp]),
+    ("fpta_healpix_pix2ang_ring", _c_int, [_i32, _i64, _vp, _vp, _vp]),
+    ("fpta_orf_anisotropic", _c_int, [_ctx_p, _i32, _vp, _i32, _i32, _vp, _vp]),
+    ("fpta_orf_plan", _c_int, [_i32, _i32, _i64, _i32, _i64, _vp]),
     ("fpta_white_accumulate", _c_int, [_ctx_p, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_gp_covariance", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_noise_wiener", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -111,18 +114,21 @@ OPT_SYNTH_PATH, OPT_MFMA_MIN_REAL, OPT_PROFILE, OPT_ANCHOR, OPT_VALU_VARIANT, OP
 OPT_GRID_WIDTH, OPT_GRID_SIGMA, OPT_GRID_MFMA, OPT_FUSE_CHECKSUMS = 7, 8, 9, 10
 OPT_MIX_MFMA, OPT_OVERLAP, OPT_INTERP_LDS, OPT_GRID_COALESCE, OPT_INTERP_WS, OPT_SIDE_SPLIT = 11, 12, 13, 14, 15, 16
 OPT_DFT_GEN, OPT_GEN_MIX, OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR = 17, 18, 19, 20, 21, 22
-OPT_INTERP_FUSED, OPT_FUSED_NEXT_MIX, OPT_CW_SPLIT = 23, 25, 26  # key 24 is retired
+OPT_INTERP_FUSED, OPT_FUSED_NEXT_MIX, OPT_CW_SPLIT, OPT_ORF_SPLIT = 23, 25, 26, 27  # key 24 is retired
 OPTIONS = (OPT_SYNTH_PATH, OPT_MFMA_MIN_REAL, OPT_PROFILE, OPT_ANCHOR, OPT_VALU_VARIANT, OPT_FUSE_WHITE,
            OPT_GRID_WIDTH, OPT_GRID_SIGMA, OPT_GRID_MFMA, OPT_FUSE_CHECKSUMS, OPT_MIX_MFMA, OPT_OVERLAP,
            OPT_INTERP_LDS, OPT_GRID_COALESCE, OPT_INTERP_WS, OPT_SIDE_SPLIT, OPT_DFT_GEN, OPT_GEN_MIX,
            OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR, OPT_INTERP_FUSED, OPT_FUSED_NEXT_MIX,
-           OPT_CW_SPLIT)
+           OPT_CW_SPLIT, OPT_ORF_SPLIT)
 K_GEN, K_MIX, K_SYNTH, K_WHITE, K_DENSE, K_GRID, K_CW, K_EPHEM = 0, 1, 2, 3, 4, 5, 6, 7
 CW_NPAR = 9  # FPTA_CW_NPAR: cos_gwtheta, gwphi, cos_inc, log10_mc, log10_fgw, log10_h, phase0, psi, psrterm
 EPHEM_NBODY = 14  # FPTA_EPHEM_NBODY: mass, T, then (value, rate per century) of inc, Om, omega, a, e, l0
 ROEMER_NPAR = 22  # FPTA_ROEMER_NPAR: a body, d_mass, d_Om, d_omega, d_inc, d_a, d_e, d_l0, 1 / mass_ss
 EPHEM_E_MAX = 0.95  # FPTA_EPHEM_E_MAX
 EPHEM_MSUN = 1.327124400e20 / 6.6743e-11  # FPTA_EPHEM_MSUN
+ORF_PLAN_LEN = 10  # FPTA_ORF_PLAN_LEN
+ORF_PLAN_KEYS = ("tile", "chunk", "map_group", "n_tiles", "n_chunks", "n_split", "chunks_per_split", "n_groups",
+                 "groups_per_launch", "workspace_bytes")
 
 
 def interp_kernel_name(code):
@@ -158,6 +164,33 @@ def build_flags():
 
 class FptaError(RuntimeError):
     pass
+
+
+def pix2ang_ring(nside, ipix=None):
+    """(theta, phi) of the HEALPix RING pixels ipix (default: all 12 nside^2) (fpta_healpix_pix2ang_ring). Host only:
+    needs no context and no GPU."""
+    nside = int(nside)
+    if ipix is None:
+        if not 1 <= nside <= 1024:  # the library's own range, checked before the pixel list is sized by it
+            raise FptaError(f"fpta_healpix_pix2ang_ring failed (-22): nside {nside} outside [1, 1024]")
+        ipix = np.arange(12 * nside * nside, dtype=np.int64)
+    ipix = np.ascontiguousarray(ipix, dtype=np.int64)
+    theta, phi = np.empty(ipix.shape), np.empty(ipix.shape)
+    rc = _lib.fpta_healpix_pix2ang_ring(nside, ipix.size, _ptr(ipix), _ptr(theta), _ptr(phi))
+    if rc < 0:
+        raise FptaError(f"fpta_healpix_pix2ang_ring failed ({rc}): {_lib.fpta_last_error(None).decode()}")
+    return theta, phi
+
+
+def orf_plan(n_psr, nside, n_map=1, split=0, npix=None):
+    """The launch plan of fpta_orf_anisotropic for a shape (fpta_orf_plan), as a dict of ORF_PLAN_KEYS. Host only. It
+    also checks the shape: FptaError for a bad nside or npix != 12 nside^2."""
+    info = np.zeros(ORF_PLAN_LEN, dtype=np.int64)
+    npix = 12 * int(nside) * int(nside) if npix is None else int(npix)
+    rc = _lib.fpta_orf_plan(int(n_psr), int(nside), npix, int(n_map), int(split), _ptr(info))
+    if rc < 0:
+        raise FptaError(f"fpta_orf_plan failed ({rc}): {_lib.fpta_last_error(None).decode()}")
+    return dict(zip(ORF_PLAN_KEYS, (int(v) for v in info)))
 
 
 def _f64(a):
@@ -358,6 +391,23 @@ class Context:
         self._check(_lib.fpta_roemer_accumulate(self._h, P, _ptr(offs), _ptr(toas), _ptr(pos), len(rows), _ptr(rows),
                                                 float(sign), int(bool(separate)), _ptr(out)),
                     "fpta_roemer_accumulate")
+
+    def orf_anisotropic(self, pos, nside, h_maps, out=None):
+        """ORFs [M, P, P] of the maps h_maps [M, 12 nside^2] (HEALPix RING) for pulsars at the unit vectors pos [P, 3]
+        (fpta_orf_anisotropic). out: a contiguous float64 [M, P, P] to write into (left untouched by a refused call)."""
+        pos, h_maps = _f64(pos), _f64(h_maps)
+        if pos.ndim != 2 or pos.shape[1] != 3 or h_maps.ndim != 2:
+            raise ValueError("orf_anisotropic: expected pos [P, 3] and h_maps [M, npix]")
+        P, (M, npix) = len(pos), h_maps.shape
+        orf_plan(P, nside, M, self.get_option(OPT_ORF_SPLIT), npix=npix)  # the shape: nside, the map length
+        if out is None:
+            out = np.empty((M, P, P))
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous
+                  and out.flags.writeable and out.shape == (M, P, P)):
+            raise ValueError(f"orf_anisotropic: out must be a writable contiguous float64 array of shape {(M, P, P)}")
+        self._check(_lib.fpta_orf_anisotropic(self._h, P, _ptr(pos), int(nside), M, _ptr(h_maps), _ptr(out)),
+                    "fpta_orf_anisotropic")
+        return out
 
     def white_accumulate(self, sigma, z, residuals, blocks=None, ecorr_sigma=None, zb=None):
         sigma, z = _f64(sigma), _f64(z)

@@ -192,6 +192,10 @@ struct fpta_ctx {
   // fpta_ephem_* / fpta_roemer_accumulate (ephem.hip): TOAs (or M), the body / row table (or e), pulsar positions,
   // the 64-TOA wave table, the output (planetssb, delays, residuals or E) and sunssb
   DevBuf eph_toas, eph_tab, eph_pos, eph_waves, eph_out, eph_sun;
+  // fpta_orf_anisotropic (orf.hip): pulsar positions, the HEALPix ring table, the maps, the K-split partial tiles of
+  // one launch, the ORFs of one launch
+  DevBuf orf_pos, orf_rings, orf_h, orf_part, orf_out;
+  int64_t orf_split = 0;  // FPTA_OPT_ORF_SPLIT: 0 auto (fpta_orf::make_plan), n >= 1 forces n K-splits
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
   int32_t out_R = 0;

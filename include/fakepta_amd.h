@@ -168,6 +168,53 @@ int fpta_roemer_accumulate(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, co
                            const double* rows /* [n_row][FPTA_ROEMER_NPAR] */, double sign, int32_t separate,
                            double* out);
 
+/* Replaces fakepta/correlated_noises.py:73-89 (anisotropic: healpy's pix2ang and one antenna-pattern call per pulsar
+ * pair) for any number of maps in one call (added without a change of FPTA_VERSION: no existing call changes). This
+ * text is the specification.
+ * Pixel centres, HEALPix RING ordering, any nside >= 1 (not only powers of two). With npix = 12 nside^2,
+ * ncap = 2 nside (nside - 1) and pixel p in 0 .. npix - 1 (isqrt the integer square root, / on integers truncating):
+ *   north cap, p < ncap:             i = (1 + isqrt(1 + 2 p)) >> 1,  j = p + 1 - 2 i (i - 1),
+ *                                    z = 1 - 4 i^2 / npix,           phi = (j - 1/2) pi / (2 i)
+ *   belt, ncap <= p < npix - ncap:   q = p - ncap,  t = q / (4 nside),  i = t + nside,  j = q - 4 nside t + 1,
+ *                                    s = (1 + ((i + nside) & 1)) / 2,
+ *                                    z = (2 nside - i) 2 / (3 nside), phi = (j - s) pi / (2 nside)
+ *   south cap, otherwise:            q = npix - p,  i = (1 + isqrt(2 q - 1)) >> 1,  j = 4 i + 1 - (q - 2 i (i - 1)),
+ *                                    z = -1 + 4 i^2 / npix,          phi = (j - 1/2) pi / (2 i)
+ * cos theta = z, sin theta = sqrt((1 - z) (1 + z)); both are rounded once from long double per ring, and phi is a
+ * rational multiple of pi ((2 (j - 1) + odd) / n_ring with n_ring the ring's pixel count), so the kernels take its
+ * cosine and sine with an exact argument reduction.
+ * Antenna pattern of a pulsar with unit vector p for a pixel, the reference's expression (:50-60) kept literally:
+ *   m = (sin phi, -cos phi, 0),  n = (-z cos phi, -z sin phi, sin theta),
+ *   Omega = (-sin theta cos phi, -sin theta sin phi, -z),  D = 1 + Omega . p,
+ *   F+ = 1/2 ((m . p)^2 - (n . p)^2) / D,   Fx = (m . p) (n . p) / D.
+ * ORF (:73-89), a weighted Gram matrix of the rows [F+ | Fx]:
+ *   ORF[m][a][b] = 1.5 k_ab / npix sum_pix (F+^a F+^b + Fx^a Fx^b) h_m[pix],   k_aa = 2, k_ab = 1 (a != b).
+ * The pixel range is cut into contiguous K-splits (FPTA_OPT_ORF_SPLIT); pixels are summed in ascending order within a
+ * split and the splits in ascending order, without atomics: a repeated call is bit-identical, the matrix is exactly
+ * symmetric, and a map's result does not depend on which other maps share its call.
+ * A pulsar exactly on a pixel centre has D = 0 and 0 / 0 terms: its row and column are NaN, as the reference's antenna
+ * pattern gives; nothing else is affected. The expression is ill-conditioned near a pixel centre:
+ * against 50-digit arithmetic at nside 4 the literal fp64 evaluation is off by 4e-14 / 1.3e-10 / 1.3e-6 of the peak
+ * for a pulsar 1e-2 / 1e-4 / 1e-6 rad from a centre. A cancellation-free form in p - pixel direction is no better: the
+ * rounding of the pixel direction itself sets the error.
+ * Validated on the host before anything is uploaded or launched (FPTA_EINVAL, the message names the index, orf_out
+ * untouched): nside < 1 or > 1024; a non-finite map value (map and pixel named); a non-finite position or
+ * | |p| - 1 | > 1e-8 (pulsar named); more than 8192 pulsars. n_psr == 0 and n_map == 0 are successful no-ops. */
+/* theta = atan2(sin theta, z) and phi of n pixels. Host only, no context: works without a GPU. FPTA_EINVAL (message
+ * from fpta_last_error(NULL)) for nside outside [1, 1024] or a pixel outside [0, npix). */
+int fpta_healpix_pix2ang_ring(int32_t nside, int64_t n, const int64_t* ipix, double* theta_out, double* phi_out);
+int fpta_orf_anisotropic(fpta_ctx* ctx, int32_t n_psr, const double* pos /* [n_psr][3] */, int32_t nside,
+                         int32_t n_map, const double* h_maps /* [n_map][npix] */,
+                         double* orf_out /* [n_map][n_psr][n_psr] */);
+/* The launch plan fpta_orf_anisotropic makes for a shape, a pure function of its arguments (split: the value of
+ * FPTA_OPT_ORF_SPLIT). Host only, no context. It also checks the shape: FPTA_EINVAL (message from
+ * fpta_last_error(NULL)) for a bad nside, npix != 12 nside^2 or a count out of range. info: pulsars per tile side,
+ * pixels per chunk, maps per group, lower-triangle tiles, pixel chunks, K-splits in use, chunks per split, map groups,
+ * map groups per launch, workspace bytes. The K-splits do not depend on n_map. */
+#define FPTA_ORF_PLAN_LEN 10
+int fpta_orf_plan(int32_t n_psr, int32_t nside, int64_t npix, int32_t n_map, int64_t split,
+                  int64_t* info /* [FPTA_ORF_PLAN_LEN] */);
+
 /* Replaces fakepta/fake_pta.py:201-230 (add_white_noise), with ECORR fixed (defects D1/D2):
  *   residuals[t] += sigma[t] * z[t]  +  sum over blocks b containing t: ecorr_sigma[b] * zb[b]
  * Blocks are CSR: block_offs[n_blocks+1] into block_idx (TOA indices, any order).
@@ -472,6 +519,9 @@ int fpta_comm_gather(fpta_comm* comm, const double* send, int64_t count, double*
 #define FPTA_OPT_CW_SPLIT 26       /* fpta_cw_accumulate: 0 (default) auto: the source range is split over blocks when
                                      the TOAs alone leave the device mostly empty (a pure function of n_src and the
                                      total TOA count); n >= 1 forces n source splits (clamped to n_src). */
+#define FPTA_OPT_ORF_SPLIT 27      /* fpta_orf_anisotropic: 0 (default) auto: the pixel range is cut into K-splits
+                                     until the tiles fill the device (a pure function of n_psr and nside,
+                                     fpta_orf_plan); n >= 1 forces n K-splits (clamped to the chunk count). */
 int fpta_set_option(fpta_ctx* ctx, int32_t key, int64_t value);
 /* Current value of option `key` (same keys as fpta_set_option). */
 int fpta_get_option(fpta_ctx* ctx, int32_t key, int64_t* value);
@@ -486,7 +536,8 @@ int fpta_build_flags(void);
 #define FPTA_K_MIX 1
 #define FPTA_K_SYNTH 2
 #define FPTA_K_WHITE 3
-#define FPTA_K_DENSE 4 /* dense covariance: basis + Gram, Cholesky, solves, draws */
+#define FPTA_K_DENSE 4 /* dense covariance: basis + Gram, Cholesky, solves, draws; fpta_orf_anisotropic: one entry per
+                          launch batch (k_orf_aniso + k_orf_reduce) */
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
 #define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]) */
 #define FPTA_K_EPHEM 7 /* fpta_ephem_kepler / fpta_ephem_orbits / fpta_roemer_accumulate: one entry per call */

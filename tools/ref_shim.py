@@ -6,7 +6,8 @@ reference does not exist there). Only the modules the hot path does not use are
 stubbed:
   * enterprise.constants  -> the reference's own copy, fakepta/constants.py
   * enterprise_extensions.deterministic.cw_delay -> raises (add_cgw is out of scope)
-  * healpy.pix2ang / npix2nside -> raise (anisotropic ORF is out of scope)
+  * healpy.pix2ang / npix2nside -> raise: healpy is not installed, so the reference's own anisotropic ORF cannot be
+    run; the build's native one (fakepta_amd/orf.py) is pinned against mpmath instead (tools/gen_orf_golden.py)
 """
 import importlib.util
 import os
