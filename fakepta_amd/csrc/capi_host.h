@@ -310,9 +310,11 @@ struct fpta_ctx {
   bool red_pending = false;
   int last_path = 0;     // synthesis path of the last batch (1 direct, 2 MFMA, 3 VALU, 4 gridded)
   std::string path_reason;  // why the last batch did not take the gridded path (empty if it did)
-  // gridded path defaults: w = 15 at sigma = 1.5 (a-priori bound 1.5e-12). The measured flat-spectrum worst case at
-  // real-MJD epochs is <= ~6e-12 relative (tests/test_gpu_grid.py at the shipped defaults; the numpy model of
-  // oracle.grid_synth and the GPU agree); w = 14 (bound 9.4e-12) is refused by the auto path. sigma = 1.5 keeps the
+  // gridded path defaults: w = 15 at sigma = 1.5 (the kernel's design estimate exp(-pi w sqrt(1 - 1/sigma)) = 1.5e-12:
+  // not a bound, a single top mode is off by up to 2.8e-11 per unit coefficient, tests/test_grid_modes.py). The
+  // measured flat-spectrum worst case at real-MJD epochs is <= ~6e-12 relative (tests/test_gpu_grid.py at the shipped
+  // defaults; the numpy model of oracle.grid_synth and the GPU agree); w = 14 (estimate 9.4e-12) is refused by the
+  // auto path. sigma = 1.5 keeps the
   // grid (DFT) a quarter smaller than sigma = 2 (tools/sweep_grid.py --params, profiles/r01_sweep_wsig.txt)
   int grid_w = 15;       // gridded path: kernel width in grid cells
   int grid_sigma100 = 150;  // gridded path: oversampling x 100
@@ -412,10 +414,10 @@ int launch_block_checksums(fpta_ctx* c, bool async = false, hipStream_t* used = 
 
 // grid_host.hip
 constexpr double kGridAutoRatio = 0.5;  // auto path: gridded when it needs < half the direct FMAs
-// auto path: gridded only when the a-priori bound exp(-pi w sqrt(1 - 1/sigma)) of the width/oversampling pair is
-// within this. The measured flat-spectrum worst case is ~3-4x the bound (w = 16, sigma = 1.5: bound 2.5e-13,
-// measured <= 3.6e-12; w = 15: 1.5e-12 / 6e-12; w = 14: 9.4e-12 / 3.2e-11, refused). A forced path 4 runs any
-// accepted pair: the caller opted in, and fpta_batch_grid_info reports the bound.
+// auto path: gridded only when the design estimate exp(-pi w sqrt(1 - 1/sigma)) of the width/oversampling pair is
+// within this. The measured flat-spectrum worst case is ~3-4x the estimate, a single top mode ~18x (w = 16,
+// sigma = 1.5: estimate 2.5e-13, measured <= 3.6e-12; w = 15: 1.5e-12 / 6e-12; w = 14: 9.4e-12 / 3.2e-11, refused). A
+// forced path 4 runs any accepted pair: the caller opted in, and fpta_batch_grid_info reports the estimate.
 constexpr double kGridAutoMaxErr = 2e-12;
 int grid_build(fpta_ctx* c, Layout& L);
 int grid_part_groups(fpta_ctx* c, GridPlan& G, int32_t P, int32_t size);

@@ -14,8 +14,9 @@
 //
 // Kernel: exponential of semicircle phi(z) = exp(beta (sqrt(1 - z^2) - 1)), |z| <= 1, width w grid
 // cells, oversampling nf >= sigma (2N + 1); q_k = (2 pi / nf) / phi_hat(k) deconvolves it.
-// A-priori relative aliasing bound exp(-pi w sqrt(1 - 1/sigma)): 1.5e-12 at the default w = 15, sigma = 1.5
-// (measured flat-spectrum worst case ~4x the bound; tests/test_gpu_grid.py, tools/sweep_grid.py).
+// Design estimate of the relative aliasing error exp(-pi w sqrt(1 - 1/sigma)): 1.5e-12 at the default w = 15,
+// sigma = 1.5. Not a bound: the measured flat-spectrum worst case is ~4x the estimate (tests/test_gpu_grid.py,
+// tools/sweep_grid.py), a single top mode up to 2.8e-11 per unit coefficient (tests/test_grid_modes.py).
 // Per sample the interpolation costs sum_s rows_s FMAs (rows ~ w + cells spanned by the chunk)
 // instead of sum_s 2 N_s for the direct contraction.
 #include <hip/hip_runtime.h>

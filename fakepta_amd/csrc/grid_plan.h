@@ -120,7 +120,9 @@ struct PlanFigures {
   double grid_vals = 0.0;    // grid values per realization (sum over signals of P nf)
   double weight_bytes = 0.0; // interpolation weight tables
   double fma_direct = 0.0;   // FMAs per realization of the direct contraction
-  double err_bound = 1.0;    // a-priori relative aliasing bound of the ES kernel, exp(-pi w sqrt(1 - 1/sigma))
+  double err_bound = 1.0;    // the ES kernel's design estimate of the relative aliasing error, exp(-pi w sqrt(1 - 1/sigma)):
+                             // not a bound, a single top mode is off by up to 2.8e-11 per unit coefficient at the
+                             // shipped (15, 1.5), 18 times the estimate (tests/test_grid_modes.py)
 };
 struct HostGridPlan : PlanFigures {
   std::vector<PlanSeg> segs;
@@ -216,7 +218,7 @@ inline void plan_coalesce(const PlanLayout& L, const PlanOptions& o, HostGridPla
 // Per grid signal: the options' (w, sigma) give nf0 = sigma (2 N + 1) grid points, a multiple of 4 (the MFMA DFT
 // runs on the quarter range); it computes whole blocks of kGridDftRows rows of the quarter range, so nf1 = 4 (rows
 // of those blocks - 1) points cost it nothing more. The larger effective oversampling sigma1 = nf1 / (2 N + 1)
-// reaches the options' a-priori bound with a narrower kernel w1; the signal takes (nf1, w1) when its interpolation
+// reaches the options' design estimate with a narrower kernel w1; the signal takes (nf1, w1) when its interpolation
 // band (w + the cells a 32-TOA chunk spans) is estimated narrower. Then per (signal, TOA) the first interpolation
 // row J (unwrapped) and the offset d = u - J, u = theta / h. False: a phase is out of range.
 inline bool plan_grid_sizes(const PlanLayout& L, const PlanOptions& o, HostGridPlan& H) {

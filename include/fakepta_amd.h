@@ -329,9 +329,11 @@ int fpta_batch_info(fpta_ctx* ctx, int64_t* info);
  * out[0] synthesis path of the last batch (1 direct, 2 MFMA, 3 VALU, 4 gridded), out[1] plan usable,
  * out[2] interpolation chunks, out[3] k_grid_dft FMAs per realization, out[4] k_grid_interp FMAs per
  * realization, out[5] direct-contraction FMAs per realization, out[6] grid values per realization,
- * out[7] interpolation-weight bytes, out[8] the FPTA_OPT_GRID_MFMA mask in force, out[9] the a-priori
- * relative aliasing bound exp(-pi w sqrt(1 - 1/sigma)) of the width/oversampling options in force (auto
- * selection takes the gridded path only when it is <= 2e-12), out[10] width w, out[11] oversampling sigma,
+ * out[7] interpolation-weight bytes, out[8] the FPTA_OPT_GRID_MFMA mask in force, out[9] the exponential-of-
+ * semicircle kernel's design estimate exp(-pi w sqrt(1 - 1/sigma)) of the relative aliasing error at the
+ * width/oversampling options in force (an estimate, not a bound: a flat spectrum errs by about 4 times as much, a
+ * single top mode by up to 2.8e-11 per unit coefficient at the defaults, 18 times; tests/test_grid_modes.py; auto
+ * selection takes the gridded path only when the estimate is <= 2e-12), out[10] width w, out[11] oversampling sigma,
  * out[12] grid signals of the plan (signals after FPTA_OPT_GRID_COALESCE), out[13] layout signals, out[14]
  * mean band rows per chunk (all grid signals, padded to 4), out[15] the interpolation kernel of the last gridded
  * block: 0 none, else 1 + 4 kind + 2 (white / ECORR epilogue) + (fused partial checksums), kind 0

@@ -8,7 +8,13 @@ every partial product is exact in longdouble and the whole cycles drop out befor
 use these as the truth and the literal fp64 evaluation's own distance from them as the yardstick (tests/test_gpu_cw.py
 does the same with a stored 60-digit truth).
 
-tests/test_ld_reference.py pins common_truth and gp_truth to the reference's recorded outputs (fixtures G2, G3)."""
+tests/test_ld_reference.py pins common_truth and gp_truth to the reference's recorded outputs (fixtures G2, G3).
+
+mode_truth is the batch paths' basis itself, one mode at a time; grid_q, grid_values and grid_mode_model are the gridded
+path's algorithm in longdouble, with the deconvolution factors from an mpmath quadrature (tests/test_grid_modes.py,
+tests/test_gpu_mode_response.py)."""
+import functools
+
 import numpy as np
 
 LD = np.longdouble
@@ -117,3 +123,81 @@ def checksum_truth(block):
     """fpta_batch_checksums: per-realization (sum, sum of squares) [R][2] in longdouble."""
     x = _f64(block).astype(LD)
     return np.stack([x.sum(axis=1), (x * x).sum(axis=1)], axis=1)
+
+
+def mode_truth(f, toas, nu, idx, freqf, mask=None):
+    """The basis itself, [n_toa, N, 2] in longdouble: ch(t) cos(2 pi f_k t) and ch(t) sin(2 pi f_k t) with
+    ch = (freqf / nu)^idx, 0 where mask (None: no mask) is 0. One pulsar's TOAs and frequencies f [N]."""
+    ph = phase(f, toas)
+    ch = chromatic(freqf, nu, idx)
+    if mask is not None:
+        ch = np.where(np.asarray(mask) != 0, ch, LD(0))
+    return np.stack([np.cos(ph), np.sin(ph)], axis=2) * ch[:, None, None]
+
+
+# --------------------------------------------------------------------------- the gridded algorithm in longdouble
+# The type-2 non-uniform FFT of csrc/grid_plan.h and DESIGN.md section 5b, evaluated with no rounding that matters
+# at fp64: it differs from mode_truth by the algorithm's aliasing alone, so a device that differs from it by more than
+# fp64 rounding has a defect, whatever the aliasing allows.
+def _to_ld(x):
+    """An mpmath number as longdouble: its two leading fp64 pieces (106 bits before the sum is rounded to 64)."""
+    hi = float(x)
+    return LD(hi) + LD(float(x - hi))
+
+
+@functools.lru_cache(maxsize=None)
+def grid_q(nm, nf, w, beta):
+    """q_k = (2 pi / nf) / phi_hat(k), k = 1 .. nm, in longdouble: phi_hat(k) = alpha int_{-1}^{1} exp(beta (sqrt(1 -
+    z^2) - 1)) cos(k alpha z) dz, alpha = pi w / nf, by mpmath at 30 digits with z = sin(theta), which makes the
+    integrand analytic on [0, pi / 2] (the kernel's square-root end point would cost a Gauss rule its accuracy)."""
+    import mpmath as mp
+    with mp.workdps(30):
+        alpha, b = mp.pi * w / nf, mp.mpf(beta)
+        out = []
+        for k in range(1, nm + 1):
+            ka = k * alpha
+            val, err = mp.quad(lambda th: mp.exp(b * (mp.cos(th) - 1)) * mp.cos(ka * mp.sin(th)) * mp.cos(th),
+                               [0, mp.pi / 2], error=True)
+            assert err <= mp.mpf(10) ** -22 * abs(val), (k, err, val)  # mpmath's own estimate: far below 2^-64
+            out.append(_to_ld((2 * mp.pi / nf) / (alpha * 2 * val)))
+    q = np.array(out, dtype=LD)
+    q.flags.writeable = False
+    return q
+
+
+def grid_values(nm, nf, w, beta, q=None):
+    """(C, S) [nm][nf] in longdouble: q_k cos / sin(2 pi ((k j) mod nf) / nf). q: other deconvolution factors than
+    grid_q's (tests of the tests)."""
+    q = grid_q(nm, nf, w, float(beta)) if q is None else np.asarray(q, dtype=LD)
+    k = np.arange(1, nm + 1, dtype=np.int64)
+    ang = TWO_PI * ((k[:, None] * np.arange(nf, dtype=np.int64)[None, :]) % nf).astype(LD) / LD(nf)
+    return q[:, None] * np.cos(ang), q[:, None] * np.sin(ang)
+
+
+def grid_mode_model(f1, toas, nu, idx, freqf, mask, J, nm, nf, w, beta, values=None):
+    """The gridded algorithm's answer for mode_truth's entries with f_k = k f_1, [n_toa, nm, 2] in longdouble (the
+    second value: sum over the w terms of |term|). u = nf (f_1 t) from the exact product as phase forms it; J [n_toa]
+    the first interpolation rows the planner takes (its fp64 expression, tests/grid_model.py first_rows), so model
+    and device interpolate over the same rows; d = u - J in longdouble; weights phi((d - i) / (w / 2)) as es_weight
+    defines them, phi(z) = exp(beta (sqrt(1 - z^2) - 1)) on |z| < 1, else 0."""
+    toas = _f64(toas)
+    C, S = grid_values(nm, nf, w, beta) if values is None else values
+    J = np.asarray(J, dtype=np.int64)
+    um = LD(nf) * (phase([f1], toas)[:, 0] / TWO_PI)  # u mod nf
+    d = um - (J % nf).astype(LD)
+    d = d - LD(nf) * np.round((d - LD(w) / 2) / LD(nf))  # the representative next to J: w / 2 - 1 < d <= w / 2
+    ch = chromatic(freqf, nu, idx)
+    if mask is not None:
+        ch = np.where(np.asarray(mask) != 0, ch, LD(0))
+    val = np.zeros((len(toas), nm, 2), dtype=LD)
+    tot = np.zeros((len(toas), nm, 2), dtype=LD)
+    for i in range(w):
+        z = (d - LD(i)) / (LD(w) / 2)
+        s = 1 - z * z
+        wt = np.where(s > 0, ch * np.exp(LD(beta) * (np.sqrt(np.maximum(s, LD(0))) - 1)), LD(0))
+        r = (J + i) % nf
+        for c, tab in enumerate((C, S)):
+            term = wt[:, None] * tab[:, r].T
+            val[:, :, c] += term
+            tot[:, :, c] += np.abs(term)
+    return val, tot

@@ -16,6 +16,7 @@ from tests.helpers import oracle_segments
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
+C4_KERNEL = "k_grid_fused<8, false, false, false>"  # no draws in the kernel (one mixed common signal), whole-chunk bands
 
 
 @pytest.fixture(scope="module")
@@ -55,6 +56,10 @@ def test_c4_ska_scale(ctx, factor):
     ctx.batch_add_signal(1, f, amp, idx=0.0, L=L)
     out_none, co = ctx.batch_synth(seed, 0, R, to_host=False, coeffs=True)
     assert out_none is None and co.shape == (P, 2 * N, R)
+    # the interpolation kernel this call ran: with the coefficient download not the instance of the C4 measurement
+    # (tools/bench_configs.py c4 runs plain blocks: below)
+    kernel_coeffs = ctx.batch_grid_info()["interp_kernel"]
+    assert kernel_coeffs == "k_grid_interp_ws<false>", kernel_coeffs
     picks = [0, 255]
     rows = np.concatenate([ctx.batch_download(r, 1) for r in picks])
     sub = [0, 1, 333, 999] if factor == "svd" else [0, 1, 63, 64, 511, 512, 999]  # triangular tile edges
@@ -73,6 +78,11 @@ def test_c4_ska_scale(ctx, factor):
     sums = ctx.batch_checksums()
     assert np.all(np.isfinite(sums)) and sums.shape == (R, 2)
     np.testing.assert_allclose(sums[picks, 1], (rows ** 2).sum(1), rtol=1e-9)
+    # a plain block, as the C4 measurement runs it: the same instance, the same samples
+    ctx.batch_synth(seed, 0, R, to_host=False)
+    kernel_plain = ctx.batch_grid_info()["interp_kernel"]
+    assert kernel_plain == C4_KERNEL, kernel_plain
+    np.testing.assert_array_equal(np.concatenate([ctx.batch_download(r, 1) for r in picks]), rows)
 
 
 def test_c5_mixed(ctx):

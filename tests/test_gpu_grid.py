@@ -3,8 +3,10 @@
 The gridded path evaluates the same Fourier sums as the direct kernels through an oversampled
 phase grid (real DFT) and a banded exponential-of-semicircle interpolation.
 It is an approximation with a bounded aliasing error: at the shipped defaults (width 15,
-oversampling 1.5; a-priori bound exp(-pi w sqrt(1 - 1/sigma)) = 1.5e-12) the error is <= ~6e-12
-relative for a FLAT spectrum (every mode weighs equally, the worst case) and smaller for red
+oversampling 1.5; the exponential-of-semicircle kernel's design estimate exp(-pi w sqrt(1 - 1/sigma)) = 1.5e-12, which
+is not a bound: a single top mode is off by up to 2.8e-11 per unit coefficient, tests/test_grid_modes.py and
+tests/test_gpu_mode_response.py) the error is <= ~6e-12
+relative for a FLAT spectrum (every mode weighs equally, the worst case of the norm) and smaller for red
 spectra (width 14 reaches 3.1e-11 on these cases: tools/grid_width_errors.py, profiles/r03l_grid_width_errors.jsonl).
 Tolerance: the suite's
 1e-10; the accuracy tests below also check the tighter bound GRID_TOL the defaults are
@@ -117,7 +119,7 @@ def test_width_and_oversampling_options(gridded, capi):
 
 def test_auto_path_respects_error_bound(ctx, capi, shipped):
     """Auto selection (path 0) takes the gridded path at the shipped defaults, refuses it (and says why) when
-    the width / oversampling pair's a-priori bound exceeds 2e-11, and reports the bound in grid_info."""
+    the width / oversampling pair's design estimate exceeds 2e-12, and reports the estimate in grid_info."""
     rng = np.random.default_rng(4)
     # 2000-TOA pulsars: the gridded plan needs well under half the direct FMAs (auto's cost rule)
     offs, toas, nu = random_layout(rng, 4, (2000, 2000), ragged=False)

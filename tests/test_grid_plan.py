@@ -14,6 +14,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import grid_model
+from tests.grid_model import bound, chrom_weight, model_groups, model_sizes, model_tables, w0_rows  # noqa: F401
+
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fakepta_amd", "csrc")
 
 # the planning constants of grid_plan.h (the program prints them; test_constants compares)
@@ -281,80 +284,7 @@ def planned(tmp_path_factory):
 
 
 # ------------------------------------------------------------------------------------------------ the numpy model
-def chrom_weight(L, s):
-    """Chromatic factor (freqf / nu)^idx times the mask, per TOA."""
-    ch = np.ones(len(L["toas"])) if s["idx"] == 0.0 else (s["freqf"] / L["nu"]) ** s["idx"]
-    return ch if s["mask"] is None else np.where(s["mask"] != 0, ch, 0.0)
-
-
-def w0_rows(L, s):
-    return s["w0"] if s["kind"] == 0 else np.full(L["P"], s["w0"][0])
-
-
-def model_groups(L):
-    """A signal joins the first earlier grid signal with the same w0 on every pulsar and the same weight per TOA."""
-    members = []
-    for i, s in enumerate(L["sigs"]):
-        for m in members:
-            f = L["sigs"][m[0]]
-            if (L["coalesce"] and len(m) <= MAX_SEG and np.array_equal(w0_rows(L, s), w0_rows(L, f))
-                    and np.array_equal(chrom_weight(L, s), chrom_weight(L, f))):
-                m.append(i)
-                break
-        else:
-            members.append([i])
-    anchor = [max(m, key=lambda i: (L["sigs"][i]["nm"], -i)) for m in members]  # most modes, the first of equals
-    return members, anchor, [m[-1] for m in members]
-
-
-def bound(w, sigma):
-    return math.exp(-math.pi * w * math.sqrt(1.0 - 1.0 / sigma))
-
-
-def model_sizes(L, s):
-    """(nf, w, took the fill, the fill inequality's two sides) of a grid signal anchored at layout signal s."""
-    nm, w = s["nm"], L["w"]
-    n0 = -(-max(math.ceil(L["sigma"] * (2.0 * nm + 1.0)), 2 * w + 2) // 4) * 4
-    rho, w0p = 0.0, w0_rows(L, s)
-    for p in range(L["P"]):
-        t = L["toas"][L["offs"][p]:L["offs"][p + 1]]
-        if len(t) > 1:
-            rho += w0p[p] * (t.max() - t.min()) / float(len(t) - 1) / (2.0 * math.pi)
-    rho /= L["P"]
-    n1 = 4 * (-(-(n0 // 4 + 1) // DFT_ROWS) * DFT_ROWS - 1)
-    w1 = w  # the narrowest kernel (>= 4) that keeps the options' bound at the larger oversampling
-    while w1 > 4 and bound(w1 - 1, n1 / (2.0 * nm + 1.0)) <= bound(w, L["sigma"]):
-        w1 -= 1
-    lhs, rhs = w1 + TT * n1 * rho, w + TT * n0 * rho - 0.25
-    fill = n1 > n0 and 2 * w1 + 2 <= n1 and lhs < rhs
-    return (n1, w1, True, lhs, rhs) if fill else (n0, w, False, lhs, rhs)
-
-
-_GL = np.polynomial.legendre.leggauss(256)
-
-
-def model_tables(nm, nf, w, beta):
-    """ecos / esin [ntab][lde] = q_k cos / sin(2 pi k j / nf), j <= nf / 2, k = m + 1; q_k = (2 pi / nf) / phi_hat(k),
-    phi_hat(k) = alpha int phi(z) cos(k alpha z) dz, phi(z) = exp(beta (sqrt(1 - z^2) - 1)), alpha = pi w / nf; tq
-    [4][ntq][ldq]: j <= nf / 4, [0] cos / [1] sin of odd k, [2] / [3] of even k."""
-    x, wt = _GL
-    half, alpha = nf // 2, math.pi * w / nf
-    lde, ntab = (half // DFT_ROWS + 1) * DFT_ROWS, -(-nm // 8) * 8
-    ldq, ntq = (nf // 4 // DFT_ROWS + 1) * DFT_ROWS, -(-((nm + 1) // 2) // 8) * 8
-    k = np.arange(1, nm + 1)
-    phi = np.exp(beta * (np.sqrt(1.0 - x * x) - 1.0))
-    q = (2.0 * math.pi / nf) / (alpha * (wt * phi * np.cos(np.outer(k, alpha * x))).sum(axis=1))
-    ang = 2.0 * math.pi * (np.outer(k, np.arange(half + 1)) % nf) / nf
-    ec, es = np.zeros((ntab, lde)), np.zeros((ntab, lde))
-    ec[:nm, :half + 1] = q[:, None] * np.cos(ang)
-    es[:nm, :half + 1] = q[:, None] * np.sin(ang)
-    tq = np.zeros((4, ntq, ldq))
-    for m in range(nm):
-        tq[2 * (m & 1), m >> 1, :nf // 4 + 1] = ec[m, :nf // 4 + 1]
-        tq[2 * (m & 1) + 1, m >> 1, :nf // 4 + 1] = es[m, :nf // 4 + 1]
-    return dict(half=half, lde=lde, ntab=ntab, ldq=ldq, ntq=ntq, ecos=ec.ravel(), esin=es.ravel(), tq=tq.ravel())
-
-
+# chrom_weight, w0_rows, model_groups, model_sizes, bound and model_tables: tests/grid_model.py
 def step_rows(band, n, fq):
     """[4][fq]: band row 4 q + j at [j][q]; rows past the band's n repeat band row 0."""
     return [band[4 * q + j] if 4 * q + j < n else band[0] for j in range(4) for q in range(fq)]
@@ -475,6 +405,7 @@ def test_constants(planned):
     assert planned[1]["product"]["constants"] == [TT, ROW_CAP, VMAX, MIN_V, MAX_SEG, DFT_ROWS, GEN_TERMS, F_MAX_SIG,
                                                   F_PITCH, F_SLOT, F_DW, F_LDS_MAX, F_FQ_MIN, F_PAD_ROWS, F_HALF_TT,
                                                   F_HALF_NQ]
+    assert (grid_model.TT, grid_model.MAX_SEG, grid_model.DFT_ROWS) == (TT, MAX_SEG, DFT_ROWS)
 
 
 REFUSED = {
