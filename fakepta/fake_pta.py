@@ -32,6 +32,7 @@ import scipy.constants as sc
 
 from fakepta_amd import _capi
 from fakepta_amd import cw as _cw
+from fakepta_amd import tm as _tm
 from . import spectrum as _spectrum_module
 
 # PSD registry (fakepta/fake_pta.py:14-22): name -> function, name -> parameter names (minus f)
@@ -492,6 +493,27 @@ class Pulsar:
             self.signal_model.pop(signal)
             for key in [k for k in self.noisedict if signal in k]:
                 self.noisedict.pop(key)
+
+    # ------------------------------------------------------------------ timing-model fit (not in the reference)
+    def fit_timing_model(self, weights='white', rcond=None):
+        """Replace self.residuals by the post-fit residuals r - M (M^T W M)^+ M^T W r of the design matrix self.Mmat,
+        on the GPU, and return the rank of the fit. weights: 'white' (1 / (EFAC^2 toaerr^2 + EQUAD^2) of the
+        noisedict), None (unit) or an array [n_toa]; rcond: a column whose orthogonalised norm is <= rcond of its own
+        norm is dropped (default 1e-10). signal_model and noisedict are untouched: reconstruct_signal keeps returning
+        the pre-fit signal."""
+        return int(fit_timing_model_array([self], weights=weights, rcond=rcond)[0])
+
+
+def fit_timing_model_array(psrs, weights='white', rcond=None):
+    """Pulsar.fit_timing_model for a whole array in ONE GPU call. weights: 'white', None, an array over all TOAs or a
+    list of per-pulsar arrays. Returns the ranks [P]."""
+    offs = np.concatenate([[0], np.cumsum([len(p.toas) for p in psrs])]).astype(np.int64)
+    res = np.concatenate([np.asarray(p.residuals, dtype=np.float64) for p in psrs])
+    rank = _tm.project(offs, [p.Mmat for p in psrs], res, weights=_tm.weights_of(psrs, weights, int(offs[-1])),
+                       rcond=rcond)
+    for i, p in enumerate(psrs):
+        p.residuals = res[offs[i]:offs[i + 1]].copy()
+    return rank
 
 
 def reconstruct_array(psrs, signals=None, freqf=1400):

@@ -45,6 +45,9 @@ _SIGS = [
     ("fpta_healpix_pix2ang_ring", _c_int, [_i32, _i64, _vp, _vp, _vp]),
     ("fpta_orf_anisotropic", _c_int, [_ctx_p, _i32, _vp, _i32, _i32, _vp, _vp]),
     ("fpta_orf_plan", _c_int, [_i32, _i32, _i64, _i32, _i64, _vp]),
+    ("fpta_batch_set_timing_model", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _dbl, _vp]),
+    ("fpta_batch_project", _c_int, [_ctx_p]),
+    ("fpta_tm_project", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _dbl, _i32, _vp, _vp]),
     ("fpta_white_accumulate", _c_int, [_ctx_p, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_gp_covariance", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_noise_wiener", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -126,6 +129,7 @@ EPHEM_NBODY = 14  # FPTA_EPHEM_NBODY: mass, T, then (value, rate per century) of
 ROEMER_NPAR = 22  # FPTA_ROEMER_NPAR: a body, d_mass, d_Om, d_omega, d_inc, d_a, d_e, d_l0, 1 / mass_ss
 EPHEM_E_MAX = 0.95  # FPTA_EPHEM_E_MAX
 EPHEM_MSUN = 1.327124400e20 / 6.6743e-11  # FPTA_EPHEM_MSUN
+TM_MAX_COL = 16  # columns of one pulsar's design matrix (fpta_tm_project, fpta_batch_set_timing_model)
 ORF_PLAN_LEN = 10  # FPTA_ORF_PLAN_LEN
 ORF_PLAN_KEYS = ("tile", "chunk", "map_group", "n_tiles", "n_chunks", "n_split", "chunks_per_split", "n_groups",
                  "groups_per_launch", "workspace_bytes")
@@ -409,6 +413,42 @@ class Context:
                     "fpta_orf_anisotropic")
         return out
 
+    @staticmethod
+    def _tm_args(what, P, n, M, ncol_psr, weights):
+        """The design matrix [n, n_col], column counts [P] or None and weights [n] or None of a timing-model call, as
+        contiguous arrays of the C types."""
+        M = _f64(M)
+        if M.ndim != 2 or M.shape[0] != n or M.shape[1] > TM_MAX_COL:
+            raise ValueError(f"{what}: M must be [{n}, n_col <= {TM_MAX_COL}], got {M.shape}")
+        if ncol_psr is not None:
+            ncol_psr = np.ascontiguousarray(ncol_psr, dtype=np.int32)
+            if ncol_psr.shape != (P,):
+                raise ValueError(f"{what}: ncol_psr must hold {P} column counts")
+        if weights is not None:
+            weights = _f64(weights)
+            if weights.shape != (n,):
+                raise ValueError(f"{what}: weights must hold {n} values")
+        return M, ncol_psr, weights
+
+    def tm_project(self, offs, M, res, ncol_psr=None, weights=None, rcond=None):
+        """The weighted least-squares fit of the design matrices M [n_toa, n_col] (pulsar p: rows offs[p] ..
+        offs[p + 1], its leading ncol_psr[p] columns) removed from every row of res [n_vec, n_toa] or [n_toa], in place
+        (fpta_tm_project). Returns the ranks [P]."""
+        offs = np.ascontiguousarray(offs, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1:
+            raise ValueError("tm_project: offs must be [P + 1]")
+        P, n = len(offs) - 1, int(offs[-1])
+        M, ncol_psr, weights = self._tm_args("tm_project", P, n, M, ncol_psr, weights)
+        if not (isinstance(res, np.ndarray) and res.dtype == np.float64 and res.flags.c_contiguous
+                and res.flags.writeable and res.ndim in (1, 2) and res.shape[-1] == n):
+            raise ValueError(f"tm_project: res must be a writable contiguous float64 array [n_vec, {n}] or [{n}]")
+        n_vec = 1 if res.ndim == 1 else res.shape[0]
+        rank = np.zeros(P, dtype=np.int32)
+        self._check(_lib.fpta_tm_project(self._h, P, _ptr(offs), _ptr(M), M.shape[1], _ptr(ncol_psr), _ptr(weights),
+                                         0.0 if rcond is None else float(rcond), n_vec, _ptr(res), _ptr(rank)),
+                    "fpta_tm_project")
+        return rank
+
     def white_accumulate(self, sigma, z, residuals, blocks=None, ecorr_sigma=None, zb=None):
         sigma, z = _f64(sigma), _f64(z)
         n = len(sigma)
@@ -448,6 +488,26 @@ class Context:
             es = _f64(ecorr_sigma)
         self._check(_lib.fpta_batch_set_white(self._h, _ptr(s), nb, _ptr(bo), _ptr(bi), _ptr(es)),
                     "fpta_batch_set_white")
+
+    def batch_set_timing_model(self, M, ncol_psr=None, weights=None, rcond=None):
+        """The timing model of the batch layout: M [n_toa, n_col] in the layout's TOA order, None or zero columns to
+        clear it (fpta_batch_set_timing_model). Returns the ranks [P]."""
+        info = self.batch_info()
+        P, n = info["n_psr"], info["n_toa"]
+        rank = np.zeros(P, dtype=np.int32)
+        if P == 0:  # no layout to check M against: the library's own state error
+            raise FptaError("fpta_batch_set_timing_model failed (-77): set_timing_model: set_toas first")
+        if M is None:
+            M = np.zeros((n, 0))
+        M, ncol_psr, weights = self._tm_args("batch_set_timing_model", P, n, M, ncol_psr, weights)
+        self._check(_lib.fpta_batch_set_timing_model(self._h, M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
+                                                     0.0 if rcond is None else float(rcond), _ptr(rank)),
+                    "fpta_batch_set_timing_model")
+        return rank
+
+    def batch_project(self):
+        """Remove the timing-model fit from the last block, in place on the device (fpta_batch_project)."""
+        self._check(_lib.fpta_batch_project(self._h), "fpta_batch_project")
 
     def batch_clear(self):
         self._check(_lib.fpta_batch_clear_signals(self._h), "fpta_batch_clear_signals")

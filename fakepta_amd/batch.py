@@ -15,6 +15,7 @@ the oracle (oracle/fakepta_oracle.py: batch_synth) restates the exact semantics.
 import numpy as np
 
 from . import _capi
+from . import tm as _tm
 from fakepta.correlated_noises import orf_factor, orf_matrix
 
 GP_NAMES = ("red_noise", "dm_gp", "chrom_gp")
@@ -65,6 +66,7 @@ class BatchSimulator:
         self.toas = np.concatenate([p.toas for p in psrs])
         self.freqs = np.concatenate([p.freqs for p in psrs])
         self.ctx.batch_set_toas(self.offs, self.toas, self.freqs)
+        self._has_tm = False  # set_timing_model
         self.segments = []  # (name, kind, f, amp, idx, L, mask) — host copy for checking/reporting
         names = signals
         if names is None:
@@ -146,9 +148,53 @@ class BatchSimulator:
     def n_toa(self):
         return int(self.offs[-1])
 
-    def synth(self, n_real, seed=0, real0=0, to_host=True, coeffs=False):
-        """Realizations real0 .. real0+n_real-1: returns [n_real, n_toa] (host) or None (device only)."""
-        return self.ctx.batch_synth(seed, real0, n_real, to_host=to_host, coeffs=coeffs)
+    def synth(self, n_real, seed=0, real0=0, to_host=True, coeffs=False, fit=False):
+        """Realizations real0 .. real0+n_real-1: returns [n_real, n_toa] (host) or None (device only). fit=True removes
+        the timing-model fit (set_timing_model) from the block on the device before the download: the returned array
+        and the resident block are post-fit."""
+        if not fit:
+            return self.ctx.batch_synth(seed, real0, n_real, to_host=to_host, coeffs=coeffs)
+        if not self._has_tm:
+            raise ValueError("synth(fit=True): no timing model is set; call set_timing_model() first")
+        got = self.ctx.batch_synth(seed, real0, n_real, to_host=False, coeffs=coeffs)
+        self.ctx.batch_project()
+        out = self.ctx.batch_download(0, n_real) if to_host else None
+        return (out, got[1]) if coeffs else out
+
+    def set_timing_model(self, Mmats=None, weights="white", rcond=None):
+        """Set the timing model that project() and synth(fit=True) remove from a block: for every pulsar the weighted
+        least-squares fit r - M (M^T W M)^+ M^T W r of its design matrix. Returns the ranks [P].
+
+        Mmats:   list of per-pulsar design matrices [n_p, m_p <= 16] (default: each pulsar's Mmat); an empty list or
+                 matrices without columns clear the model.
+        weights: "white" (default) 1 / (EFAC^2 toaerr^2 + EQUAD^2) from each pulsar's noisedict, None for unit
+                 weights, or an array [n_toa] (or a list of per-pulsar arrays).
+        rcond:   a column whose orthogonalised norm is <= rcond of its own norm is dropped (default 1e-10).
+
+        The weights are diagonal: ECORR is not part of them, and a generalised least-squares fit against a dense
+        covariance is out of scope."""
+        if Mmats is None:
+            Mmats = [p.Mmat for p in self.psrs]
+        Mmats = list(Mmats)
+        if len(Mmats) not in (0, len(self.psrs)):
+            raise ValueError(f"set_timing_model: {len(Mmats)} design matrices for {len(self.psrs)} pulsars")
+        if not Mmats:
+            Mmats = [np.zeros((len(p.toas), 0)) for p in self.psrs]
+        for i, (m, p) in enumerate(zip(Mmats, self.psrs)):
+            if np.ndim(m) != 2 or np.shape(m)[0] != len(p.toas):
+                raise ValueError(f"set_timing_model: design matrix of pulsar {i} must be [{len(p.toas)}, n_col], got "
+                                 f"shape {np.shape(m)}")
+        M, ncol = _tm.stack_design(Mmats)
+        w = _tm.weights_of(self.psrs, weights, self.n_toa)
+        self._has_tm = False
+        rank = self.ctx.batch_set_timing_model(M, ncol_psr=ncol, weights=w, rcond=rcond)
+        self._has_tm = M.shape[1] > 0
+        return rank
+
+    def project(self):
+        """Remove the timing-model fit from the last block, in place on the device: checksums(), correlations(),
+        hd_curve() and downloads afterwards see post-fit residuals. The next synth() is not affected."""
+        self.ctx.batch_project()
 
     def synth_from_z(self, z):
         """Validation mode: z [n_real, n_seg, P, N_max, 2] standard normals (cos, sin)."""

@@ -1352,6 +1352,7 @@ int fpta_batch_set_toas(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const d
   if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   c->has_sigma = c->has_blocks = false;
+  c->has_tm = false;  // the timing model's tables are per TOA of the layout they were set for
   c->out_R = 0;
   return layout_set_toas(c, c->batch, n_psr, offs, toas, nu);
 }

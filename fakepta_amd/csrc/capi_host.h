@@ -196,6 +196,11 @@ struct fpta_ctx {
   // one launch, the ORFs of one launch
   DevBuf orf_pos, orf_rings, orf_h, orf_part, orf_out;
   int64_t orf_split = 0;  // FPTA_OPT_ORF_SPLIT: 0 auto (fpta_orf::make_plan), n >= 1 forces n K-splits
+  // timing-model projection (tm.hip): the batch layout's basis Q [n_toa][16], s = sqrt(w), CSR offsets and ranks
+  // (fpta_batch_set_timing_model; has_tm: a model is set), and the same tables plus the residuals of one
+  // fpta_tm_project call
+  DevBuf tm_q, tm_s, tm_offs, tm_rank, tm1_q, tm1_s, tm1_offs, tm1_rank, tm1_res;
+  bool has_tm = false;
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
   int32_t out_R = 0;

@@ -215,6 +215,39 @@ int fpta_orf_anisotropic(fpta_ctx* ctx, int32_t n_psr, const double* pos /* [n_p
 int fpta_orf_plan(int32_t n_psr, int32_t nside, int64_t npix, int32_t n_map, int64_t split,
                   int64_t* info /* [FPTA_ORF_PLAN_LEN] */);
 
+/* ------------------------------------------------------------------ timing-model projection
+ * The weighted least-squares fit of a pulsar's timing model (the design matrix of fakepta/fake_pta.py make_Mmat; the
+ * reference never applies it) removed from residuals (added without a change of FPTA_VERSION: no existing call
+ * changes). This text is the specification.
+ * For pulsar p with n_p TOAs, design matrix M_p [n_p][m_p], 0 <= m_p <= 16, and weights w > 0, a vector r becomes
+ *   r' = r - M_p (M_p^T W M_p)^+ M_p^T W r,   W = diag(w).
+ * The normal equations are never formed. On the host, in long double: every column of W^(1/2) M_p is scaled to unit
+ * norm, then orthogonalised against the columns kept before it by modified Gram-Schmidt, twice; a column that is all
+ * zero, or whose norm after both passes is <= rcond (relative to its scaled norm, 1), is dropped. rcond <= 0 means
+ * 1e-10. The kept columns, rounded to fp64, are the basis Q_p [n_p][k_p], k_p the rank. With s = sqrt(w) (fp64) the
+ * device computes g = Q_p^T (s o r) and r' = r - (Q_p g) / s on fp64 MFMA (k_tm_project), without atomics: a vector's
+ * result is bit-identical whatever the number of vectors of the call, its position among them and its neighbours.
+ * A pulsar of rank 0 keeps its samples bit for bit. weights NULL: unit weights. ncol_psr NULL: every pulsar uses all
+ * n_col columns; else pulsar p uses the leading ncol_psr[p] <= n_col columns of its rows. rank_out NULL or [n_psr].
+ * Validated on the host before anything is uploaded or launched (FPTA_EINVAL, the message names the pulsar, TOA and
+ * column): n_col outside [0, 16], a column count outside [0, n_col], a non-finite entry in a column in use, a weight
+ * that is not positive and finite. Kernel time is booked under FPTA_K_DENSE, one entry per call.
+ *
+ * fpta_batch_set_timing_model: the model of the batch layout (after fpta_batch_set_toas, else FPTA_ESTATE); M is
+ *   [n_toa_total][n_col] row-major in the layout's TOA order. n_col == 0 clears the model, and so does
+ *   fpta_batch_set_toas.
+ * fpta_batch_project: projects the context's last block in place on the context's stream (FPTA_ESTATE without a block
+ *   or without a model). fpta_batch_download, _checksums and _correlations afterwards see the post-fit block; the next
+ *   block is not affected. Blocks streamed by fpta_batch_synth_checksums / fpta_multi_synth are not projected.
+ * fpta_tm_project: one call for any array, independent of the batch layout: res [n_vec][offs[n_psr]] in and out. A
+ *   pulsar may have no TOAs. */
+int fpta_batch_set_timing_model(fpta_ctx* ctx, int32_t n_col, const double* M /* [n_toa_total][n_col] */,
+                                const int32_t* ncol_psr, const double* weights, double rcond, int32_t* rank_out);
+int fpta_batch_project(fpta_ctx* ctx);
+int fpta_tm_project(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const double* M /* [n_toa_total][n_col] */,
+                    int32_t n_col, const int32_t* ncol_psr, const double* weights, double rcond, int32_t n_vec,
+                    double* res /* [n_vec][n_toa_total] */, int32_t* rank_out);
+
 /* Replaces fakepta/fake_pta.py:201-230 (add_white_noise), with ECORR fixed (defects D1/D2):
  *   residuals[t] += sigma[t] * z[t]  +  sum over blocks b containing t: ecorr_sigma[b] * zb[b]
  * Blocks are CSR: block_offs[n_blocks+1] into block_idx (TOA indices, any order).
@@ -538,7 +571,8 @@ int fpta_build_flags(void);
 #define FPTA_K_MIX 1
 #define FPTA_K_SYNTH 2
 #define FPTA_K_WHITE 3
-#define FPTA_K_DENSE 4 /* dense covariance: basis + Gram, Cholesky, solves, draws; fpta_orf_anisotropic: one entry per
+#define FPTA_K_DENSE 4 /* dense covariance: basis + Gram, Cholesky, solves, draws; k_tm_project: one entry per call
+                        * (fpta_batch_project, fpta_tm_project); fpta_orf_anisotropic: one entry per
                           launch batch (k_orf_aniso + k_orf_reduce) */
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
 #define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]) */
