@@ -32,6 +32,7 @@ import scipy.constants as sc
 
 from fakepta_amd import _capi
 from fakepta_amd import cw as _cw
+from fakepta_amd import fit as _fit
 from fakepta_amd import tm as _tm
 from . import spectrum as _spectrum_module
 
@@ -502,6 +503,42 @@ class Pulsar:
         norm is dropped (default 1e-10). signal_model and noisedict are untouched: reconstruct_signal keeps returning
         the pre-fit signal."""
         return int(fit_timing_model_array([self], weights=weights, rcond=rcond)[0])
+
+    # ------------------------------------------------------------------ Fourier fit (not in the reference)
+    def fit_fourier(self, components=30, idx=0., weights='white', marginalize_tm=True, rcond=None, freqf=1400):
+        """Fit Fourier coefficients to self.residuals on the GPU: (f [N], coeffs [2, N]) in the convention of
+        signal_model[...]['fourier'] (row 0 cosines, row 1 sines, amplitude / df with df = diff(append(0, f))), so
+        that reconstruct_signal's sum over them is the fitted signal. components: a mode count (f = k / Tspan) or an
+        array of frequencies; idx: the chromatic index, columns (freqf / freqs)^idx cos / sin(2 pi f t); weights as
+        fit_timing_model; marginalize_tm: fit self.Mmat jointly and discard its part. A column the rank rule drops
+        (fewer TOAs than columns, f = 1 / yr beside the annual columns) has coefficient 0. residuals and
+        signal_model are untouched."""
+        return fit_fourier_array([self], components=components, idx=idx, weights=weights,
+                                 marginalize_tm=marginalize_tm, rcond=rcond, freqf=freqf)[0]
+
+
+def fit_fourier_array(psrs, components=30, idx=0., weights='white', marginalize_tm=True, rcond=None, freqf=1400):
+    """Pulsar.fit_fourier for a whole array in ONE GPU call; each pulsar is fitted on its own grid k / Tspan (or on
+    the given frequencies). Returns a list of (f, coeffs [2, N]) per pulsar."""
+    offs = np.concatenate([[0], np.cumsum([len(p.toas) for p in psrs])]).astype(np.int64)
+    toas = np.concatenate([np.asarray(p.toas, dtype=np.float64) for p in psrs])
+    nu = np.concatenate([np.asarray(p.freqs, dtype=np.float64) for p in psrs])
+    res = np.concatenate([np.asarray(p.residuals, dtype=np.float64) for p in psrs])
+    if np.ndim(components) == 0:
+        n = int(components)
+        if n != components or n < 1:
+            raise ValueError(f"components must be a positive mode count or an array of frequencies, got {components!r}")
+        f = np.stack([np.arange(1, n + 1) / max(p.Tspan, 1.0) for p in psrs])
+    else:
+        f = np.tile(np.asarray(components, dtype=np.float64), (len(psrs), 1))
+    n_modes, f, coef, _, _ = _fit.coefficients(
+        offs, toas, nu, [(f, idx)], res, Mmats=[p.Mmat for p in psrs] if marginalize_tm else None,
+        weights=_tm.weights_of(psrs, weights, int(offs[-1])), rcond=rcond, common=False, freqf=freqf)
+    out = []
+    for i in range(len(psrs)):
+        df = _fit.delta_f(f[i])
+        out.append((f[i].copy(), np.vstack((coef[i, :n_modes[0], 0], coef[i, n_modes[0]:, 0])) / df))
+    return out
 
 
 def fit_timing_model_array(psrs, weights='white', rcond=None):

@@ -48,6 +48,12 @@ _SIGS = [
     ("fpta_batch_set_timing_model", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _dbl, _vp]),
     ("fpta_batch_project", _c_int, [_ctx_p]),
     ("fpta_tm_project", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _dbl, _i32, _vp, _vp]),
+    ("fpta_batch_set_fit", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _dbl, _vp, _vp]),
+    ("fpta_batch_fit_info", _c_int, [_ctx_p, _vp]),
+    ("fpta_batch_fit", _c_int, [_ctx_p, _vp]),
+    ("fpta_batch_fit_cross", _c_int, [_ctx_p, _vp]),
+    ("fpta_fit_coefficients", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
+                                       _vp, _dbl, _i32, _vp, _vp, _vp, _vp]),
     ("fpta_white_accumulate", _c_int, [_ctx_p, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_gp_covariance", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_noise_wiener", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -130,6 +136,7 @@ ROEMER_NPAR = 22  # FPTA_ROEMER_NPAR: a body, d_mass, d_Om, d_omega, d_inc, d_a,
 EPHEM_E_MAX = 0.95  # FPTA_EPHEM_E_MAX
 EPHEM_MSUN = 1.327124400e20 / 6.6743e-11  # FPTA_EPHEM_MSUN
 TM_MAX_COL = 16  # columns of one pulsar's design matrix (fpta_tm_project, fpta_batch_set_timing_model)
+FIT_MAX_COMP, FIT_MAX_COEF = 4, 512  # components and Fourier columns of one fit (fpta_batch_set_fit)
 ORF_PLAN_LEN = 10  # FPTA_ORF_PLAN_LEN
 ORF_PLAN_KEYS = ("tile", "chunk", "map_group", "n_tiles", "n_chunks", "n_split", "chunks_per_split", "n_groups",
                  "groups_per_launch", "workspace_bytes")
@@ -508,6 +515,111 @@ class Context:
     def batch_project(self):
         """Remove the timing-model fit from the last block, in place on the device (fpta_batch_project)."""
         self._check(_lib.fpta_batch_project(self._h), "fpta_batch_project")
+
+    @staticmethod
+    def _fit_args(what, P, n_modes, f, idx, freqf):
+        """The component tables of a Fourier-fit call as contiguous arrays of the C types: n_modes [n_comp] int32, f
+        [sum N_c] (common) or [P, sum N_c], idx and freqf [n_comp]. Returns them and whether f is common."""
+        n_modes = np.ascontiguousarray(n_modes, dtype=np.int32)
+        if n_modes.ndim != 1 or not 1 <= len(n_modes) <= FIT_MAX_COMP or np.any(n_modes < 1):
+            raise ValueError(f"{what}: n_modes must hold 1 .. {FIT_MAX_COMP} positive mode counts, got {n_modes}")
+        n_f = int(n_modes.sum())
+        if 2 * n_f > FIT_MAX_COEF:
+            raise ValueError(f"{what}: {2 * n_f} Fourier columns, more than {FIT_MAX_COEF}")
+        f = _f64(f)
+        if f.shape not in ((n_f,), (P, n_f)):
+            raise ValueError(f"{what}: f must be [{n_f}] or [{P}, {n_f}], got {f.shape}")
+        idx, freqf = _f64(idx), _f64(freqf)
+        if idx.shape != n_modes.shape or freqf.shape != n_modes.shape:
+            raise ValueError(f"{what}: idx and freqf must hold one value per component")
+        return n_modes, f, idx, freqf, f.ndim == 1
+
+    def batch_set_fit(self, n_modes, f, idx, freqf, M=None, ncol_psr=None, weights=None, rcond=None):
+        """The Fourier fit of the batch layout (fpta_batch_set_fit): components of n_modes[c] frequencies (f: one grid
+        [sum N_c] for the array or [P, sum N_c]) with chromatic index idx[c] at freqf[c]; M [n_toa, n_col] the
+        nuisance design that is marginalised (None: nothing). n_modes None or empty clears the fit. Returns
+        (kept Fourier columns [P], kept mask [P, K] bool)."""
+        info = self.batch_info()
+        P, n = info["n_psr"], info["n_toa"]
+        rank = np.zeros(P, dtype=np.int32)
+        if P == 0 or n_modes is None or len(n_modes) == 0:  # without a layout: the library's own state error
+            self._check(_lib.fpta_batch_set_fit(self._h, 0, None, None, 1, None, None, 0, None, None, None, 0.0,
+                                                _ptr(rank), None), "fpta_batch_set_fit")
+            return rank, np.zeros((P, 0), dtype=bool)
+        n_modes, f, idx, freqf, common = self._fit_args("batch_set_fit", P, n_modes, f, idx, freqf)
+        if M is None:
+            M = np.zeros((n, 0))
+        M, ncol_psr, weights = self._tm_args("batch_set_fit", P, n, M, ncol_psr, weights)
+        kept = np.zeros((P, 2 * int(n_modes.sum())), dtype=np.uint8)
+        self._check(_lib.fpta_batch_set_fit(self._h, len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx),
+                                            _ptr(freqf), M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
+                                            0.0 if rcond is None else float(rcond), _ptr(rank), _ptr(kept)),
+                    "fpta_batch_set_fit")
+        return rank, kept.astype(bool)
+
+    def batch_fit_info(self):
+        """K and mode count of the fit that is set (0: none), whether its grid is common, and the realizations of the
+        last fit result (fpta_batch_fit_info)."""
+        info = np.zeros(4, dtype=np.int64)
+        self._check(_lib.fpta_batch_fit_info(self._h, _ptr(info)), "fpta_batch_fit_info")
+        return dict(K=int(info[0]), n_mode=int(info[1]), common=bool(info[2]), n_real=int(info[3]))
+
+    def batch_fit(self, K=None, to_host=True):
+        """Fit the last block (fpta_batch_fit): [P, K, R] on the host, or None with the result left on the device.
+        The buffer is sized from the library's own K; a K given here is only checked against it."""
+        have = self.batch_fit_info()["K"]
+        if K is not None and have and int(K) != have:
+            raise ValueError(f"batch_fit: the fit that is set has {have} Fourier columns, not {K}")
+        if not to_host:
+            self._check(_lib.fpta_batch_fit(self._h, None), "fpta_batch_fit")
+            return None
+        try:
+            _, _, R = self.batch_device_out()
+        except FptaError:
+            R = 0  # no block: the library's state error follows
+        out = np.empty((self.batch_info()["n_psr"], have, R))
+        self._check(_lib.fpta_batch_fit(self._h, _ptr(out)), "fpta_batch_fit")
+        return out
+
+    def batch_fit_cross(self, n_mode=None):
+        """[n_mode, P, P]: per mode the sum over the last fit's realizations of cos_a cos_b + sin_a sin_b
+        (fpta_batch_fit_cross; a common grid only). The buffer is sized from the library's own mode count; an n_mode
+        given here is only checked against it."""
+        have = self.batch_fit_info()["n_mode"]
+        if n_mode is not None and have and int(n_mode) != have:
+            raise ValueError(f"batch_fit_cross: the fit that is set has {have} modes, not {n_mode}")
+        P = self.batch_info()["n_psr"]
+        out = np.empty((have, P, P))
+        self._check(_lib.fpta_batch_fit_cross(self._h, _ptr(out)), "fpta_batch_fit_cross")
+        return out
+
+    def fit_coefficients(self, offs, toas, nu, n_modes, f, idx, freqf, res, M=None, ncol_psr=None, weights=None,
+                         rcond=None):
+        """The Fourier coefficients of every row of res [n_vec, n_toa] or [n_toa] for any array
+        (fpta_fit_coefficients). Returns (coef [P, K, n_vec], kept Fourier columns [P], kept mask [P, K] bool)."""
+        offs = np.ascontiguousarray(offs, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1:
+            raise ValueError("fit_coefficients: offs must be [P + 1]")
+        P, n = len(offs) - 1, int(offs[-1])
+        toas, nu, res = _f64(toas), _f64(nu), _f64(res)
+        if toas.shape != (n,) or nu.shape != (n,):
+            raise ValueError(f"fit_coefficients: toas and nu must hold {n} values")
+        if res.ndim not in (1, 2) or res.shape[-1] != n:
+            raise ValueError(f"fit_coefficients: res must be [n_vec, {n}] or [{n}], got {res.shape}")
+        n_vec = 1 if res.ndim == 1 else res.shape[0]
+        n_modes, f, idx, freqf, common = self._fit_args("fit_coefficients", P, n_modes, f, idx, freqf)
+        if M is None:
+            M = np.zeros((n, 0))
+        M, ncol_psr, weights = self._tm_args("fit_coefficients", P, n, M, ncol_psr, weights)
+        K = 2 * int(n_modes.sum())
+        coef = np.zeros((P, K, n_vec))
+        rank, kept = np.zeros(P, dtype=np.int32), np.zeros((P, K), dtype=np.uint8)
+        self._check(_lib.fpta_fit_coefficients(self._h, P, _ptr(offs), _ptr(toas), _ptr(nu), len(n_modes),
+                                               _ptr(n_modes), _ptr(f), int(common), _ptr(idx), _ptr(freqf),
+                                               M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
+                                               0.0 if rcond is None else float(rcond), n_vec, _ptr(res), _ptr(coef),
+                                               _ptr(rank), _ptr(kept)), "fpta_fit_coefficients")
+        return coef, rank, kept.astype(bool)
 
     def batch_clear(self):
         self._check(_lib.fpta_batch_clear_signals(self._h), "fpta_batch_clear_signals")

@@ -15,6 +15,7 @@ the oracle (oracle/fakepta_oracle.py: batch_synth) restates the exact semantics.
 import numpy as np
 
 from . import _capi
+from . import fit as _fit
 from . import tm as _tm
 from fakepta.correlated_noises import orf_factor, orf_matrix
 
@@ -67,6 +68,7 @@ class BatchSimulator:
         self.freqs = np.concatenate([p.freqs for p in psrs])
         self.ctx.batch_set_toas(self.offs, self.toas, self.freqs)
         self._has_tm = False  # set_timing_model
+        self._fit = None  # set_fourier_fit: dict(n_modes, f, idx, freqf, common)
         self.segments = []  # (name, kind, f, amp, idx, L, mask) — host copy for checking/reporting
         names = signals
         if names is None:
@@ -196,6 +198,73 @@ class BatchSimulator:
         hd_curve() and downloads afterwards see post-fit residuals. The next synth() is not affected."""
         self.ctx.batch_project()
 
+    # ------------------------------------------------------------------ Fourier fit
+    def set_fourier_fit(self, components=None, Mmats="tm", weights="white", rcond=None, common=None):
+        """Set the Fourier fit that fourier_fit(), power_spectrum(), cross_spectrum() and hd_curve(domain="fourier")
+        apply to a block: for every pulsar the joint weighted least squares of a nuisance design and Fourier columns,
+        of which the Fourier amplitudes come back. Returns (kept Fourier columns [P], kept mask [P, K]).
+
+        components: a list of 1 .. 4 entries, each a signal name of this layout (its f and idx), (n_modes, idx) for
+                 the grid k / Tspan of the array, or (f, idx) with f [N] or [P, N]. Default: one achromatic component
+                 of 30 modes at k / Tspan. A component's columns are (freqf / nu)^idx cos(2 pi f_k t), k = 0 .. N - 1,
+                 then the sines: the order of signal_model[...]['fourier'].
+        Mmats:   "tm" (default) marginalises each pulsar's Mmat, None nothing, or a list of per-pulsar matrices
+                 [n_p, m_p <= 16].
+        weights: as set_timing_model. rcond: a column whose orthogonalised norm is <= rcond is dropped, its
+                 coefficient 0 (default 1e-10).
+        common:  None keeps one frequency grid for the array when every component has one; True insists on it;
+                 False gives every pulsar its own copy (cross_spectrum() then refuses)."""
+        tspan = float(np.ptp(self.toas)) if len(self.toas) else 0.0
+        n_modes, f, idx, freqf = _fit.resolve_components(components, len(self.psrs), tspan, self.segments, common)
+        if isinstance(Mmats, str):
+            if Mmats != "tm":
+                raise ValueError(f"set_fourier_fit: Mmats must be 'tm', None or a list of matrices, got {Mmats!r}")
+            Mmats = [p.Mmat for p in self.psrs]
+        if Mmats is None:
+            Mmats = [np.zeros((len(p.toas), 0)) for p in self.psrs]
+        Mmats = list(Mmats)
+        if len(Mmats) != len(self.psrs):
+            raise ValueError(f"set_fourier_fit: {len(Mmats)} design matrices for {len(self.psrs)} pulsars")
+        for i, (m, p) in enumerate(zip(Mmats, self.psrs)):
+            if np.ndim(m) != 2 or np.shape(m)[0] != len(p.toas):
+                raise ValueError(f"set_fourier_fit: design matrix of pulsar {i} must be [{len(p.toas)}, n_col], got "
+                                 f"shape {np.shape(m)}")
+        M, ncol = _tm.stack_design(Mmats)
+        w = _tm.weights_of(self.psrs, weights, self.n_toa)
+        self._fit = None
+        rank, kept = self.ctx.batch_set_fit(n_modes, f, idx, freqf, M=M, ncol_psr=ncol, weights=w, rcond=rcond)
+        self._fit = dict(n_modes=n_modes, f=f, idx=idx, freqf=freqf, common=f.ndim == 1)
+        return rank, kept
+
+    def _need_fit(self, what):
+        if self._fit is None:
+            raise ValueError(f"{what}: no Fourier fit is set; call set_fourier_fit() first")
+        return self._fit
+
+    def fourier_fit(self, to_host=True):
+        """The Fourier coefficients of the last block, [P, K, R] in the units of the residuals (None with
+        to_host=False: the result stays on the device for cross_spectrum()). The block is untouched."""
+        fit = self._need_fit("fourier_fit")
+        return self.ctx.batch_fit(2 * int(fit["n_modes"].sum()), to_host=to_host)
+
+    def power_spectrum(self):
+        """Per component [P, N_c]: the mean over the last block's realizations of (a_cos^2 + a_sin^2) / (2 df), df =
+        diff(append(0, f)): the units of signal_model[...]['psd'], so it compares with spectrum.powerlaw directly."""
+        fit = self._need_fit("power_spectrum")
+        return _fit.power_spectrum(self.fourier_fit(), fit["n_modes"], fit["f"])
+
+    def cross_spectrum(self, psd=True):
+        """[sum N_c, P, P]: per mode the mean over the last block's realizations of a_cos^a a_cos^b + a_sin^a a_sin^b,
+        divided by 2 df (power_spectrum's units; its diagonal is power_spectrum()) unless psd=False. Fitted and
+        contracted on the device; a common frequency grid only."""
+        fit = self._need_fit("cross_spectrum")
+        if not fit["common"]:
+            raise ValueError("cross_spectrum: the fit has per-pulsar frequencies; a common grid is needed")
+        self.ctx.batch_fit(2 * int(fit["n_modes"].sum()), to_host=False)
+        _, _, R = self.ctx.batch_device_out()
+        X = self.ctx.batch_fit_cross(int(fit["n_modes"].sum())) / R
+        return X / (2.0 * _fit.mode_delta_f(fit["n_modes"], fit["f"]))[:, None, None] if psd else X
+
     def synth_from_z(self, z):
         """Validation mode: z [n_real, n_seg, P, N_max, 2] standard normals (cos, sin)."""
         return self.ctx.batch_synth_from_z(z)
@@ -207,14 +276,25 @@ class BatchSimulator:
         _, _, R = self.ctx.batch_device_out()
         return self.ctx.batch_correlations(2 if normalized else 1) / R
 
-    def hd_curve(self, bins=10, estimator="ratio", return_counts=False):
+    def hd_curve(self, bins=10, estimator="ratio", return_counts=False, domain="time"):
         """(mean, std, bin centres) of the pairwise correlations against angular separation
         (correlated_noises.py:21-47) for the last block. estimator "ratio": mean cross-power over
         sqrt(mean auto-powers) (consistent); "per_realization": mean of per-realization normalized
         correlations (biased toward 0 by O(1/n_eff) for red processes). A bin with no pulsar pair is NaN,
         as the reference's bin_curve gives, but without NumPy's empty-slice warnings; return_counts=True
-        appends the number of pairs per bin so callers can mask the empty ones."""
-        if estimator == "ratio":
+        appends the number of pairs per bin so callers can mask the empty ones. domain "fourier" (estimator "ratio"
+        only) takes the correlations from the Fourier fit (set_fourier_fit) instead of the zero-lag dot product: S =
+        the sum over modes of cross_spectrum(psd=False), binned as S[a][b] / sqrt(S[a][a] S[b][b]); it needs no
+        common TOA count, so it works for ragged arrays."""
+        if domain not in ("time", "fourier"):
+            raise ValueError(f"hd_curve: domain must be 'time' or 'fourier', got {domain!r}")
+        if domain == "fourier":
+            if estimator != "ratio":
+                raise ValueError("hd_curve: domain 'fourier' has the 'ratio' estimator only")
+            S = self.cross_spectrum(psd=False).sum(axis=0)
+            d = np.sqrt(np.diag(S))
+            C = S / np.outer(d, d)
+        elif estimator == "ratio":
             C = self.correlations(normalized=False)
             d = np.sqrt(np.diag(C))
             C = C / np.outer(d, d)

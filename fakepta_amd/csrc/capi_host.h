@@ -201,6 +201,13 @@ struct fpta_ctx {
   // fpta_tm_project call
   DevBuf tm_q, tm_s, tm_offs, tm_rank, tm1_q, tm1_s, tm1_offs, tm1_rank, tm1_res;
   bool has_tm = false;
+  // Fourier fit (fit.hip): the batch layout's operators (pulsar p's A_p [K][n_p] at K offs[p]), CSR offsets, kept-column
+  // counts and the cosine / sine row of every mode (fpta_batch_set_fit; has_fit: a fit is set), the coefficients
+  // [P][K][fit_rpad] of the last fpta_batch_fit (fit_R realizations; 0: none) and the cross-spectra of one
+  // fpta_batch_fit_cross; the same tables plus the residuals and coefficients of one fpta_fit_coefficients call
+  DevBuf fit_a, fit_offs, fit_rank, fit_rows, fit_coef, fit_x, fit1_a, fit1_offs, fit1_rank, fit1_res, fit1_coef;
+  bool has_fit = false, fit_common = false;
+  int32_t fit_K = 0, fit_modes = 0, fit_R = 0, fit_rpad = 0;
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
   int32_t out_R = 0;

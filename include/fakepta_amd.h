@@ -248,6 +248,67 @@ int fpta_tm_project(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const dou
                     int32_t n_col, const int32_t* ncol_psr, const double* weights, double rcond, int32_t n_vec,
                     double* res /* [n_vec][n_toa_total] */, int32_t* rank_out);
 
+/* ------------------------------------------------------------------ Fourier fit
+ * The Fourier coefficients of residuals: the adjoint of the synthesis, residual block -> per-pulsar, per-realization
+ * amplitudes, and the cross-spectrum of an array from them (added without a change of FPTA_VERSION: no existing call
+ * changes). This text is the specification.
+ * For pulsar p with n_p >= 0 TOAs t, radio frequencies nu and weights w > 0 the model is r = M_p b + F_p a:
+ *   M_p [n_p][m_p], 0 <= m_p <= 16, a nuisance design (the timing model, say), marginalised and not returned;
+ *   F_p [n_p][K], K = sum_c 2 N_c <= 512, the columns of 1 .. 4 components in order. Component c has N_c >= 1
+ *   frequencies f_c, all positive and finite, a chromatic index idx_c and a reference frequency freqf_c; its columns
+ *   are (freqf_c / nu)^idx_c cos(2 pi f_c[k] t), k = 0 .. N_c - 1, then (freqf_c / nu)^idx_c sin(2 pi f_c[k] t): the
+ *   order of signal_model[...]['fourier'] (fakepta/fake_pta.py:385-387). idx_c == 0: the factor is 1 and nu is not
+ *   read. f is [sum_c N_c] for the whole array (f_is_common != 0) or [n_psr][sum_c N_c].
+ * The fit is the joint weighted least squares min |W^(1/2) (r - M_p b - F_p a)|^2, W = diag(w); the result is
+ * a [K], in the units of r. The normal equations are never formed. On the host, in long double (cos / sin of the
+ * long-double argument): every column of W^(1/2) [M_p F_p] is scaled to unit norm; the columns are taken in order,
+ * M_p's first, and orthogonalised against the kept ones by modified Gram-Schmidt, twice; a column that is all zero,
+ * or whose norm after both passes is <= rcond, is dropped. rcond <= 0 means 1e-10. A dropped Fourier column has
+ * coefficient exactly 0 and a 0 in the kept mask: a pulsar with fewer TOAs than columns, or a frequency of 1 / yr
+ * beside annual nuisance columns, drops columns instead of failing. With W^(1/2) [M_p F_p]_kept = Q R the inverse of R
+ * is upper triangular, so a_kept = R_FF^-1 Q_F^T (s o r), s = sqrt(w): the host forms A_p = R_FF^-1 Q_F^T diag(s)
+ * (with the column scaling undone), [K][n_p], zero rows for dropped columns, rounds it once to fp64 and uploads it;
+ * the device computes a = A_p r on fp64 MFMA (k_fit_apply) and nothing else, without atomics: a vector's coefficients
+ * are bit-identical whatever the number of vectors of the call, its position among them and its neighbours. The
+ * operator takes 8 K n_toa_total bytes on the host and on the device; an allocation that fails is FPTA_ENOMEM with
+ * the size in the message. weights NULL: unit weights. ncol_psr NULL: every pulsar uses all n_col columns of M
+ * [n_toa_total][n_col]; else pulsar p the leading ncol_psr[p]. rank_out (NULL or [n_psr]) gets the number of kept
+ * Fourier columns, kept_out (NULL or [n_psr][K]) the kept mask.
+ * Validated on the host before anything is uploaded or launched (FPTA_EINVAL; the message names the pulsar, TOA,
+ * column, component or mode): n_col outside [0, 16], a column count outside [0, n_col], a non-finite entry in a column
+ * in use, a weight that is not positive and finite, n_comp outside [1, 4], N_c < 1, K > 512, a frequency that is not
+ * positive and finite, a non-finite idx, a non-finite epoch, and with idx_c != 0 a freqf_c or a nu that is not positive
+ * and finite. Kernel time is booked under FPTA_K_DENSE, one entry per call.
+ *
+ * fpta_batch_set_fit: the fit of the batch layout (after fpta_batch_set_toas, else FPTA_ESTATE), with the layout's
+ *   TOAs and radio frequencies. n_comp == 0 clears it, and so does fpta_batch_set_toas. Independent of
+ *   fpta_batch_set_timing_model.
+ * fpta_batch_fit: fits the context's last block on the context's stream (FPTA_ESTATE without a block or without a
+ *   fit). The block is read only: what is computed from it, and every later block, is unaffected. The result stays on
+ *   the device as [n_psr][K][R_pad], realizations contiguous; coef_host NULL or [n_psr][K][n_real].
+ * fpta_batch_fit_cross: from the last fpta_batch_fit result (FPTA_ESTATE without one), for a common grid only
+ *   (FPTA_EINVAL otherwise): out [sum_c N_c][n_psr][n_psr],
+ *     X[m][a][b] = sum over the block's realizations of (a_cos^a a_cos^b + a_sin^a a_sin^b) of mode m,
+ *   modes in component order, as a Gram on fp64 MFMA (k_fit_cross): the lower triangle computed and mirrored, in a
+ *   fixed order, bit-symmetric. The caller divides by the realization count and accumulates across blocks.
+ * fpta_fit_coefficients: one call for any array, independent of the batch layout: res [n_vec][offs[n_psr]],
+ *   coef_out [n_psr][K][n_vec]. A pulsar may have no TOAs: its coefficients are zero. */
+int fpta_batch_set_fit(fpta_ctx* ctx, int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                       const double* idx, const double* freqf, int32_t n_col,
+                       const double* M /* [n_toa_total][n_col] */, const int32_t* ncol_psr, const double* weights,
+                       double rcond, int32_t* rank_out, uint8_t* kept_out);
+/* info[0] = K of the fit that is set (0: none), info[1] = sum_c N_c, info[2] = 1 for a common grid, info[3] = the
+ * realizations of the last fpta_batch_fit result (0: none): what sizes coef_host and fpta_batch_fit_cross's out. */
+int fpta_batch_fit_info(fpta_ctx* ctx, int64_t* info /* [4] */);
+int fpta_batch_fit(fpta_ctx* ctx, double* coef_host);
+int fpta_batch_fit_cross(fpta_ctx* ctx, double* out);
+int fpta_fit_coefficients(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const double* toas, const double* nu,
+                          int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                          const double* idx, const double* freqf, int32_t n_col,
+                          const double* M /* [n_toa_total][n_col] */, const int32_t* ncol_psr, const double* weights,
+                          double rcond, int32_t n_vec, const double* res /* [n_vec][n_toa_total] */,
+                          double* coef_out /* [n_psr][K][n_vec] */, int32_t* rank_out, uint8_t* kept_out);
+
 /* Replaces fakepta/fake_pta.py:201-230 (add_white_noise), with ECORR fixed (defects D1/D2):
  *   residuals[t] += sigma[t] * z[t]  +  sum over blocks b containing t: ecorr_sigma[b] * zb[b]
  * Blocks are CSR: block_offs[n_blocks+1] into block_idx (TOA indices, any order).
@@ -572,7 +633,8 @@ int fpta_build_flags(void);
 #define FPTA_K_SYNTH 2
 #define FPTA_K_WHITE 3
 #define FPTA_K_DENSE 4 /* dense covariance: basis + Gram, Cholesky, solves, draws; k_tm_project: one entry per call
-                        * (fpta_batch_project, fpta_tm_project); fpta_orf_anisotropic: one entry per
+                        * (fpta_batch_project, fpta_tm_project); k_fit_apply and k_fit_cross: one entry per call
+                        * (fpta_batch_fit, fpta_fit_coefficients, fpta_batch_fit_cross); fpta_orf_anisotropic: one entry per
                           launch batch (k_orf_aniso + k_orf_reduce) */
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
 #define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]) */
