@@ -39,6 +39,7 @@ _SIGS = [
     ("fpta_common_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp,
                                         _vp]),
     ("fpta_cw_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _dbl, _vp]),
+    ("fpta_batch_cw_accumulate", _c_int, [_ctx_p, _vp, _vp, _i64, _i32, _vp, _vp, _dbl]),
     ("fpta_ephem_kepler", _c_int, [_ctx_p, _i64, _vp, _vp, _vp]),
     ("fpta_ephem_orbits", _c_int, [_ctx_p, _i64, _vp, _i32, _vp, _vp, _vp]),
     ("fpta_roemer_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _dbl, _i32, _vp]),
@@ -362,6 +363,35 @@ class Context:
         self._check(_lib.fpta_cw_accumulate(self._h, P, _ptr(offs), _ptr(toas), _ptr(pos), _ptr(pdist_s),
                                             len(sources), _ptr(sources), float(sign), _ptr(residuals)),
                     "fpta_cw_accumulate")
+
+    def batch_cw_accumulate(self, pos, pdist_s, n_tab, src_offs, sources, sign=1.0):
+        """Continuous waves added to every realization of the last batch block, in place on the device
+        (fpta_batch_cw_accumulate). pos [P, 3] and pdist_s [P] or [R, P] (light-seconds) for the batch layout's
+        pulsars; n_tab 1 (one table for all) or R tables in CSR form: table r is sources[src_offs[r]:src_offs[r + 1]],
+        rows of CW_NPAR values (fakepta_amd.cw.population_tables makes the three)."""
+        P = self.batch_info()["n_psr"]
+        if P == 0:  # no layout to check the shapes against: the library's own state error
+            raise FptaError("fpta_batch_cw_accumulate failed (-77): batch_cw_accumulate: set_toas first")
+        pos, pdist_s = _f64(pos), _f64(pdist_s)
+        src_offs = np.ascontiguousarray(src_offs, dtype=np.int64)
+        sources = _f64(sources).reshape(-1, CW_NPAR)
+        n_tab = int(n_tab)
+        if pos.shape != (P, 3) or pdist_s.ndim not in (1, 2) or pdist_s.shape[-1] != P:
+            raise ValueError(f"batch_cw_accumulate: expected pos [{P}, 3] and pdist_s [{P}] or [n_real, {P}], got "
+                             f"{pos.shape} and {pdist_s.shape}")
+        if pdist_s.ndim == 2:
+            try:
+                _, _, R = self.batch_device_out()
+            except FptaError:
+                R = pdist_s.shape[0]  # no block: the library's state error follows
+            if pdist_s.shape[0] != R:
+                raise ValueError(f"batch_cw_accumulate: pdist_s for {pdist_s.shape[0]} realizations, the block has {R}")
+        if n_tab < 0 or src_offs.shape != (n_tab + 1,) or (len(src_offs) and src_offs[-1] != len(sources)):
+            raise ValueError(f"batch_cw_accumulate: src_offs must hold {n_tab + 1} offsets ending at the "
+                             f"{len(sources)} source rows")
+        self._check(_lib.fpta_batch_cw_accumulate(self._h, _ptr(pos), _ptr(pdist_s), P if pdist_s.ndim == 2 else 0,
+                                                  n_tab, _ptr(src_offs), _ptr(sources), float(sign)),
+                    "fpta_batch_cw_accumulate")
 
     def ephem_kepler(self, M, e):
         """E with E - e sin E = M, elementwise (fpta_ephem_kepler); M and e broadcast against each other."""

@@ -198,6 +198,41 @@ class BatchSimulator:
         hd_curve() and downloads afterwards see post-fit residuals. The next synth() is not affected."""
         self.ctx.batch_project()
 
+    # ------------------------------------------------------------------ continuous waves
+    def add_cgw(self, sources, sign=1.0, p_dist=None):
+        """Add continuous waves of circular binaries (fakepta_amd.cw, the signal of Pulsar.add_cgw) to every
+        realization of the last block, in place on the device: downloads, checksums(), correlations(), hd_curve(),
+        project() and fourier_fit() afterwards see the block with the waves. The next synth() is not affected.
+
+        sources: one table for every realization ([S, 9] rows of cw.COLUMNS, or a dict keyed by Pulsar.add_cgw's
+                 argument names), or one population per realization: an [R, S, 9] array or a list of R tables
+                 [S_r, 9] (cw.population_tables); a table may be empty.
+        sign:    -1.0 takes the same waves out again (to rounding).
+        p_dist:  None: every pulsar at L = light_seconds(p.pdist). An array [P] or [R, P]: L =
+                 light_seconds(p.pdist, p_dist), the distance draws (in units of the distance's sigma) of a pulsar-term
+                 study, one per pulsar or one per (realization, pulsar).
+
+        Every pulsar needs pos and pdist. A bad source (named by realization and index) or a missing block raises the
+        library's error and leaves the block as it was."""
+        from . import cw as _cw
+        P = len(self.psrs)
+        try:
+            pos = np.array([np.asarray(p.pos, dtype=np.float64) for p in self.psrs]).reshape(P, 3)
+            pdist = [p.pdist for p in self.psrs]
+        except AttributeError as e:
+            raise ValueError(f"add_cgw: every pulsar needs pos and pdist ({e})") from None
+        _, _, R = self.ctx.batch_device_out()  # the library's state error without a block
+        n_tab, src_offs, src = _cw.population_tables(sources, R)
+        if p_dist is None:
+            L = np.array([_cw.light_seconds(d) for d in pdist], dtype=np.float64)
+        else:
+            p_dist = np.asarray(p_dist, dtype=np.float64)
+            if p_dist.shape not in ((P,), (R, P)):
+                raise ValueError(f"add_cgw: p_dist must be [{P}] or [{R}, {P}], got {p_dist.shape}")
+            L = np.stack([np.broadcast_to(_cw.light_seconds(d, p_dist[..., i]), p_dist.shape[:-1])
+                          for i, d in enumerate(pdist)], axis=-1)
+        self.ctx.batch_cw_accumulate(pos, L, n_tab, src_offs, src, sign=sign)
+
     # ------------------------------------------------------------------ Fourier fit
     def set_fourier_fit(self, components=None, Mmats="tm", weights="white", rcond=None, common=None):
         """Set the Fourier fit that fourier_fit(), power_spectrum(), cross_spectrum() and hd_curve(domain="fourier")

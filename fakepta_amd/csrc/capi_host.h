@@ -189,6 +189,10 @@ struct fpta_ctx {
   // tables, the 64-TOA wave table, partial sums [n_split][n_toa]
   DevBuf cw_toas, cw_pos, cw_L, cw_ev, cw_gm, cw_pair, cw_waves, cw_part;
   int64_t cw_split = 0;  // FPTA_OPT_CW_SPLIT: 0 auto (fpta_cw::split_count), n >= 1 forces n source splits
+  // fpta_batch_cw_accumulate (cw_batch.hip): pulsar positions, light-travel times [P] or [R][P], the CSR offsets of the
+  // source tables, the per-source tables of all realizations, the 256-TOA slab table, and the delay vector [n_toa] of
+  // the one-table mode
+  DevBuf cwb_pos, cwb_L, cwb_offs, cwb_ev, cwb_gm, cwb_slabs, cwb_v;
   // fpta_ephem_* / fpta_roemer_accumulate (ephem.hip): TOAs (or M), the body / row table (or e), pulsar positions,
   // the 64-TOA wave table, the output (planetssb, delays, residuals or E) and sunssb
   DevBuf eph_toas, eph_tab, eph_pos, eph_waves, eph_out, eph_sun;

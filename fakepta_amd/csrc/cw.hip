@@ -9,26 +9,12 @@
 //                cache, and the pulsar-term branch is uniform. No LDS, no atomics.
 //   k_cw_reduce  with n_split > 1 the source range is cut into n_split contiguous pieces (blockIdx.y), each writing
 //                its partial sums; this kernel adds them into the residuals in ascending piece order.
+// The arithmetic of a pair and of a source at a TOA is cw_device.h's, which cw_batch.hip shares.
 #include "capi_host.h"
-#include "cw_host.h"
+#include "cw_device.h"
 #include "device_common.h"
 
 namespace __attribute__((visibility("hidden"))) capi {
-
-using fpta_cw::SrcEval;
-using fpta_cw::SrcGeom;
-
-struct CwPair {
-  double Es, Ec;  // sign a0 (F+ Ps + Fx Xs), sign a0 (F+ Pc + Fx Xc)
-  double shift;   // L (1 - cos mu): the pulsar term is evaluated at t - shift
-  double pad;
-};
-
-struct CwWave {
-  int64_t first;  // first TOA (index into the concatenated arrays)
-  int32_t psr;
-  int32_t count;  // 1 .. 64
-};
 
 constexpr int kCwWave = 64;
 
@@ -39,30 +25,7 @@ __global__ __launch_bounds__(256) void k_cw_prep(const SrcGeom* __restrict__ gm,
   if (i >= (int64_t)n_psr * n_src) return;
   const int32_t p = (int32_t)(i / n_src), s = (int32_t)(i - (int64_t)p * n_src);
   FPTA_DCHECK(p < n_psr, "k_cw_prep pulsar", p, n_psr);
-  const SrcGeom g = gm[s];
-  const double px = pos[3 * p], py = pos[3 * p + 1], pz = pos[3 * p + 2];
-  // m = (sin phi, -cos phi, 0), n = (-cos th cos phi, -cos th sin phi, sin th), omhat = (-sin th cos phi,
-  // -sin th sin phi, -cos th)
-  const double mp = g.sph * px - g.cph * py;
-  const double nq = -g.cth * g.cph * px - g.cth * g.sph * py + g.sth * pz;
-  const double op = -g.sth * g.cph * px - g.sth * g.sph * py - g.cth * pz;
-  const double fplus = 0.5 * (mp * mp - nq * nq) / (1.0 + op);
-  const double fcross = (mp * nq) / (1.0 + op);
-  CwPair o;
-  o.Es = sign * (fplus * g.Ps + fcross * g.Xs);
-  o.Ec = sign * (fplus * g.Pc + fcross * g.Xc);
-  o.shift = Ls[p] * (1.0 + op);  // cos mu = -op
-  o.pad = 0.0;
-  pair[i] = o;
-}
-
-// alpha(x) (Es sin 2 phase(x) + Ec cos 2 phase(x)) without the amplitude a0 (folded into Es, Ec)
-__device__ __forceinline__ double cw_term(const SrcEval& e, double Es, double Ec, double x) {
-  const double l = log1p(-e.K * x);
-  const double ph2 = 2.0 * (e.hp0 - e.C * expm1(0.625 * l));
-  double sn, cs;
-  sincos(ph2, &sn, &cs);
-  return exp(0.125 * l) * (Es * sn + Ec * cs);
+  pair[i] = cw_pair(gm[s], pos[3 * p], pos[3 * p + 1], pos[3 * p + 2], Ls[p], sign);
 }
 
 // dst: the residuals (SPLIT false: read and written) or the partial sums [gridDim.y][n_toa] (SPLIT true: written)
@@ -84,9 +47,7 @@ __global__ __launch_bounds__(kCwWave) void k_cw_main(const CwWave* __restrict__ 
   for (int32_t s = s0; s < s1; ++s) {
     const SrcEval e = ev[s];
     const CwPair q = pr[s];
-    double d = -cw_term(e, q.Es, q.Ec, t);
-    if (e.pterm != 0.0) d += cw_term(e, q.Es, q.Ec, t - q.shift);
-    acc += d;
+    acc += cw_delay(e, q.Es, q.Ec, q.shift, t);
   }
   if ((int32_t)threadIdx.x < w.count) {
     if (SPLIT)
@@ -103,6 +64,62 @@ __global__ __launch_bounds__(256) void k_cw_reduce(const double* __restrict__ pa
   double acc = 0.0;
   for (int32_t k = 0; k < n_split; ++k) acc += part[(int64_t)k * n_toa + i];
   res[i] += acc;
+}
+
+// The device part of a call, shared with fpta_batch_cw_accumulate's one-table mode (cw_batch.hip): cw_prepare makes
+// the wave table and the split of (n_src, n_toa, option) and queues every upload but the TOAs and the residuals;
+// cw_launch queues k_cw_prep, k_cw_main and, with more than one piece, k_cw_reduce on the ctx stream. Nothing is
+// validated here.
+int cw_prepare(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const double* pos, const double* pdist_s,
+               const std::vector<SrcEval>& ev, const std::vector<SrcGeom>& gm, CwRun& r) {
+  const int64_t n_toa = offs[n_psr];
+  const int32_t n_src = (int32_t)ev.size();
+  std::vector<CwWave>& waves = r.waves;  // the caller keeps it until the stream has taken the upload
+  waves.clear();
+  for (int32_t p = 0; p < n_psr; ++p)
+    for (int64_t i = offs[p]; i < offs[p + 1]; i += kCwWave)
+      waves.push_back({i, p, (int32_t)std::min<int64_t>(kCwWave, offs[p + 1] - i)});
+  if (waves.size() > (size_t)0x7FFFFFFF) return fail(c, FPTA_EINVAL, "cw_accumulate: too many TOAs");
+  const int32_t n_split = fpta_cw::split_count(n_src, n_toa, c->cw_split);
+  r.n_psr = n_psr;
+  r.n_src = n_src;
+  r.n_toa = n_toa;
+  r.per_split = (n_src + n_split - 1) / n_split;
+  r.n_used = (n_src + r.per_split - 1) / r.per_split;  // no empty trailing piece
+  int rc;
+  if ((rc = upload(c, c->cw_pos, pos, sizeof(double) * 3 * n_psr, "cw pos"))) return rc;
+  if ((rc = upload(c, c->cw_L, pdist_s, sizeof(double) * n_psr, "cw pdist"))) return rc;
+  if ((rc = upload(c, c->cw_ev, ev.data(), sizeof(SrcEval) * ev.size(), "cw sources"))) return rc;
+  if ((rc = upload(c, c->cw_gm, gm.data(), sizeof(SrcGeom) * gm.size(), "cw source geometry"))) return rc;
+  if ((rc = upload(c, c->cw_waves, waves.data(), sizeof(CwWave) * waves.size(), "cw waves"))) return rc;
+  HIPCHK(c, c->cw_pair.ensure(sizeof(CwPair) * (size_t)n_psr * (size_t)n_src), "cw pair table");
+  if (r.n_used > 1) HIPCHK(c, c->cw_part.ensure(sizeof(double) * (size_t)r.n_used * n_toa), "cw partial sums");
+  return FPTA_OK;
+}
+
+// toas, res: device [n_toa]; res is read and written (res += sign * the sum over the sources)
+int cw_launch(fpta_ctx* c, const CwRun& r, const double* toas, double sign, double* res) {
+  const int64_t n_pair = (int64_t)r.n_psr * r.n_src;
+  k_cw_prep<<<dim3((unsigned)((n_pair + 255) / 256)), dim3(256), 0, c->stream>>>(
+      c->cw_gm.as<SrcGeom>(), c->cw_pos.as<double>(), c->cw_L.as<double>(), r.n_psr, r.n_src, sign,
+      c->cw_pair.as<CwPair>());
+  HIPCHK(c, hipGetLastError(), "k_cw_prep launch");
+  const dim3 grid((unsigned)r.waves.size(), (unsigned)r.n_used);
+  if (r.n_used > 1) {
+    k_cw_main<true><<<grid, dim3(kCwWave), 0, c->stream>>>(c->cw_waves.as<CwWave>(), toas, c->cw_ev.as<SrcEval>(),
+                                                          c->cw_pair.as<CwPair>(), r.n_src, r.per_split, r.n_toa,
+                                                          c->cw_part.as<double>());
+    HIPCHK(c, hipGetLastError(), "k_cw_main launch");
+    k_cw_reduce<<<dim3((unsigned)((r.n_toa + 255) / 256)), dim3(256), 0, c->stream>>>(c->cw_part.as<double>(), r.n_used,
+                                                                                     r.n_toa, res);
+    HIPCHK(c, hipGetLastError(), "k_cw_reduce launch");
+  } else {
+    k_cw_main<false><<<grid, dim3(kCwWave), 0, c->stream>>>(c->cw_waves.as<CwWave>(), toas, c->cw_ev.as<SrcEval>(),
+                                                           c->cw_pair.as<CwPair>(), r.n_src, r.per_split, r.n_toa,
+                                                           res);
+    HIPCHK(c, hipGetLastError(), "k_cw_main launch");
+  }
+  return FPTA_OK;
 }
 
 }  // namespace capi
@@ -133,48 +150,15 @@ extern "C" int fpta_cw_accumulate(fpta_ctx* c, int32_t n_psr, const int64_t* off
   std::string why;
   const int64_t bad = fpta_cw::validate_sources(n_src, src, tmax, ev.data(), gm.data(), why);
   if (bad >= 0) return fail(c, FPTA_EINVAL, "cw_accumulate: source " + std::to_string(bad) + ": " + why);
-  std::vector<CwWave> waves;
-  for (int32_t p = 0; p < n_psr; ++p)
-    for (int64_t i = offs[p]; i < offs[p + 1]; i += kCwWave)
-      waves.push_back({i, p, (int32_t)std::min<int64_t>(kCwWave, offs[p + 1] - i)});
-  if (waves.size() > (size_t)0x7FFFFFFF) return fail(c, FPTA_EINVAL, "cw_accumulate: too many TOAs");
-  const int32_t n_split = fpta_cw::split_count(n_src, n_toa, c->cw_split);
-  const int32_t per_split = (n_src + n_split - 1) / n_split;
-  const int32_t n_used = (n_src + per_split - 1) / per_split;  // no empty trailing piece
-
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   int rc;
+  CwRun run;
   if ((rc = upload(c, c->cw_toas, toas, sizeof(double) * n_toa, "cw toas"))) return rc;
-  if ((rc = upload(c, c->cw_pos, pos, sizeof(double) * 3 * n_psr, "cw pos"))) return rc;
-  if ((rc = upload(c, c->cw_L, pdist_s, sizeof(double) * n_psr, "cw pdist"))) return rc;
-  if ((rc = upload(c, c->cw_ev, ev.data(), sizeof(SrcEval) * ev.size(), "cw sources"))) return rc;
-  if ((rc = upload(c, c->cw_gm, gm.data(), sizeof(SrcGeom) * gm.size(), "cw source geometry"))) return rc;
-  if ((rc = upload(c, c->cw_waves, waves.data(), sizeof(CwWave) * waves.size(), "cw waves"))) return rc;
+  if ((rc = cw_prepare(c, n_psr, offs, pos, pdist_s, ev, gm, run))) return rc;
   if ((rc = upload(c, c->scratch_out, residuals, sizeof(double) * n_toa, "cw residuals"))) return rc;
-  const int64_t n_pair = (int64_t)n_psr * n_src;
-  HIPCHK(c, c->cw_pair.ensure(sizeof(CwPair) * (size_t)n_pair), "cw pair table");
-  if (n_used > 1) HIPCHK(c, c->cw_part.ensure(sizeof(double) * (size_t)n_used * n_toa), "cw partial sums");
   {
     KTimer kt(c, FPTA_K_CW);
-    k_cw_prep<<<dim3((unsigned)((n_pair + 255) / 256)), dim3(256), 0, c->stream>>>(
-        c->cw_gm.as<SrcGeom>(), c->cw_pos.as<double>(), c->cw_L.as<double>(), n_psr, n_src, sign,
-        c->cw_pair.as<CwPair>());
-    HIPCHK(c, hipGetLastError(), "k_cw_prep launch");
-    const dim3 grid((unsigned)waves.size(), (unsigned)n_used);
-    if (n_used > 1) {
-      k_cw_main<true><<<grid, dim3(kCwWave), 0, c->stream>>>(c->cw_waves.as<CwWave>(), c->cw_toas.as<double>(),
-                                                            c->cw_ev.as<SrcEval>(), c->cw_pair.as<CwPair>(), n_src,
-                                                            per_split, n_toa, c->cw_part.as<double>());
-      HIPCHK(c, hipGetLastError(), "k_cw_main launch");
-      k_cw_reduce<<<dim3((unsigned)((n_toa + 255) / 256)), dim3(256), 0, c->stream>>>(
-          c->cw_part.as<double>(), n_used, n_toa, c->scratch_out.as<double>());
-      HIPCHK(c, hipGetLastError(), "k_cw_reduce launch");
-    } else {
-      k_cw_main<false><<<grid, dim3(kCwWave), 0, c->stream>>>(c->cw_waves.as<CwWave>(), c->cw_toas.as<double>(),
-                                                             c->cw_ev.as<SrcEval>(), c->cw_pair.as<CwPair>(), n_src,
-                                                             per_split, n_toa, c->scratch_out.as<double>());
-      HIPCHK(c, hipGetLastError(), "k_cw_main launch");
-    }
+    if ((rc = cw_launch(c, run, c->cw_toas.as<double>(), sign, c->scratch_out.as<double>()))) return rc;
   }
   HIPCHK(c, hipMemcpyAsync(residuals, c->scratch_out.p, sizeof(double) * n_toa, hipMemcpyDeviceToHost, c->stream),
          "cw download");

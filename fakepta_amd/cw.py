@@ -44,6 +44,38 @@ def source_table(sources):
     return np.ascontiguousarray(tab)
 
 
+def population_tables(sources, n_real):
+    """(n_tab, src_offs [n_tab + 1] int64, src [total, 9] float64): the source tables of a block of n_real
+    realizations in the CSR form fpta_batch_cw_accumulate takes. sources is one table for every realization ([S, 9],
+    one row, or a dict as for source_table: n_tab 1), an [n_real, S, 9] array, or a list of n_real tables [S_r, 9] of
+    any lengths (an empty one included). Needs no device."""
+    n_real = int(n_real)
+    if n_real < 1:
+        raise ValueError(f"population_tables: n_real must be >= 1, got {n_real}")
+    ncol = len(COLUMNS)
+    per_real = None
+    if isinstance(sources, dict):
+        tab = source_table(sources)
+    elif isinstance(sources, (list, tuple)) and len(sources) and all(
+            np.ndim(t) == 2 or np.size(t) == 0 for t in sources):
+        per_real = [np.zeros((0, ncol)) if np.size(t) == 0 else source_table(t) for t in sources]
+    else:
+        arr = np.asarray(sources, dtype=np.float64)
+        if arr.ndim == 3:
+            if arr.shape[2] != ncol:
+                raise ValueError(f"population_tables: sources [R, S, {ncol}] expected, got {arr.shape}")
+            per_real = list(arr)
+        else:
+            tab = source_table(arr)
+    if per_real is None:
+        return 1, np.array([0, len(tab)], dtype=np.int64), tab
+    if len(per_real) != n_real:
+        raise ValueError(f"population_tables: {len(per_real)} source tables for {n_real} realizations")
+    offs = np.concatenate([[0], np.cumsum([len(t) for t in per_real])]).astype(np.int64)
+    src = np.concatenate(per_real, axis=0) if offs[-1] else np.zeros((0, ncol))
+    return n_real, offs, np.ascontiguousarray(src, dtype=np.float64)
+
+
 def accumulate(toas_list, pos_list, L_list, sources, residuals, sign=1.0):
     """residuals (concatenated over the pulsars, float64, in place) += sign * sum over sources of the delay."""
     offs = np.concatenate([[0], np.cumsum([len(t) for t in toas_list])]).astype(np.int64)

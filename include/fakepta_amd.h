@@ -119,6 +119,28 @@ int fpta_cw_accumulate(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const 
                        const double* pos /* [n_psr][3] */, const double* pdist_s /* [n_psr] L in seconds */,
                        int32_t n_src, const double* src /* [n_src][FPTA_CW_NPAR] */,
                        double sign, double* residuals /* host fp64 [n_toa_total], read and written */);
+/* The same waves injected into the context's last batch block, in place on the device (added without a change of
+ * FPTA_VERSION: no existing call changes): for every realization r of the block and every TOA t of the batch layout,
+ *   block[r][t in p] += sign * sum_s delay(t; source s of table r, pulsar p),
+ * the delay as above, summed over s in ascending order in one register. n_tab == the block's realization count: table
+ * r is the rows src_offs[r] .. src_offs[r + 1] - 1 of src (CSR; a table may be empty), and realization r equals, bit for
+ * bit, its samples plus what fpta_cw_accumulate adds to zeros for table r in one piece (FPTA_OPT_CW_SPLIT 1). n_tab == 1:
+ * one table for every realization; with pdist_stride == 0 its delay vector is made once with fpta_cw_accumulate's own
+ * split rule (it equals that call on zeros bit for bit) and added to every realization. pos [P][3] and pdist_s are the
+ * batch layout's pulsars; pdist_stride 0: pdist_s [P] for every realization, P: pdist_s [n_real][P], one distance draw
+ * per (realization, pulsar). FPTA_ESTATE without a synthesized block. Validated on the host before anything is uploaded
+ * or launched (FPTA_EINVAL, the block untouched): n_tab not 1 or the block's realization count, src_offs not starting
+ * at 0 or not monotone, pdist_stride not 0 or P, a non-finite sign, position or distance, and every source as
+ * fpta_cw_accumulate validates it against the layout's latest TOA ("realization r, source s: reason"). No sources at
+ * all is a successful no-op. It runs on the context's stream and returns when the block is updated;
+ * fpta_batch_download, _checksums, _correlations, _project and _fit afterwards see the block with the waves; the next
+ * block is not affected. Blocks streamed by fpta_batch_synth_checksums / fpta_multi_synth get no waves. Kernel time is
+ * booked under FPTA_K_CW, one entry per call. */
+int fpta_batch_cw_accumulate(fpta_ctx* ctx, const double* pos /* [P][3] */, const double* pdist_s,
+                             int64_t pdist_stride /* 0: [P] for all, P: [n_real][P] */,
+                             int32_t n_tab /* 1: one table for every realization; else == the block's n_real */,
+                             const int64_t* src_offs /* [n_tab + 1] */,
+                             const double* src /* [src_offs[n_tab]][FPTA_CW_NPAR] */, double sign);
 
 /* Replaces fakepta/ephemeris.py (Ephemeris.solve_kepler_equation, compute_orbit, get_planet_ssb, get_sunssb,
  * roemer_delay: one scipy newton call per (TOA, body) and a Python rotation per sample) for any number of bodies and a
@@ -637,7 +659,8 @@ int fpta_build_flags(void);
                         * (fpta_batch_fit, fpta_fit_coefficients, fpta_batch_fit_cross); fpta_orf_anisotropic: one entry per
                           launch batch (k_orf_aniso + k_orf_reduce) */
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
-#define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]) */
+#define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]);
+                        * fpta_batch_cw_accumulate: one entry per call (k_cw_block, or those kernels + k_cw_bcast) */
 #define FPTA_K_EPHEM 7 /* fpta_ephem_kepler / fpta_ephem_orbits / fpta_roemer_accumulate: one entry per call */
 #define FPTA_K_N 8
 /* Accumulated launches and HIP-event milliseconds of kernel `which` since the last reset. */
