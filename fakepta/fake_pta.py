@@ -541,6 +541,21 @@ def fit_fourier_array(psrs, components=30, idx=0., weights='white', marginalize_
     return out
 
 
+def optimal_statistic_array(psrs, target=None, orfs=('hd',), bins=None, template=None, signals=None,
+                            marginalize_tm=True, weights='white', rcond=None, per_mode=False):
+    """The noise-weighted optimal cross-correlation statistic of psr.residuals for a whole array in ONE GPU call (not
+    in the reference). The noise model is what the pulsars carry: every GP of signal_model (or `signals`) with psd * df
+    as prior variance, and the white noise of the noisedict as weights; target names the common process (default: the
+    only '*common*' signal) and template its spectrum (default: the target's own psd * df, so A2 is in units of the
+    injected power). Returns a dict: A2 and snr [n_orf, 1], A2_joint for several ORFs, rho_bins [bins, 1] with
+    bin_centres and bin_counts, Q, norm (fakepta_amd.os.derive). ECORR is not part of the weights. residuals and
+    signal_model are untouched."""
+    from fakepta_amd import os as _os
+    return _os.statistic_array(psrs, target=target, orfs=orfs, bins=bins, template=template, signals=signals,
+                               Mmats='tm' if marginalize_tm else None, weights=weights, rcond=rcond,
+                               per_mode=per_mode)
+
+
 def fit_timing_model_array(psrs, weights='white', rcond=None):
     """Pulsar.fit_timing_model for a whole array in ONE GPU call. weights: 'white', None, an array over all TOAs or a
     list of per-pulsar arrays. Returns the ranks [P]."""

@@ -55,6 +55,12 @@ _SIGS = [
     ("fpta_batch_fit_cross", _c_int, [_ctx_p, _vp]),
     ("fpta_fit_coefficients", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
                                        _vp, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    ("fpta_batch_set_os", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp,
+                                   _dbl, _i32, _vp, _vp, _vp]),
+    ("fpta_batch_os_info", _c_int, [_ctx_p, _vp]),
+    ("fpta_batch_os", _c_int, [_ctx_p, _vp, _vp, _vp]),
+    ("fpta_os_statistic", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
+                                   _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_white_accumulate", _c_int, [_ctx_p, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_gp_covariance", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_noise_wiener", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -138,6 +144,7 @@ EPHEM_E_MAX = 0.95  # FPTA_EPHEM_E_MAX
 EPHEM_MSUN = 1.327124400e20 / 6.6743e-11  # FPTA_EPHEM_MSUN
 TM_MAX_COL = 16  # columns of one pulsar's design matrix (fpta_tm_project, fpta_batch_set_timing_model)
 FIT_MAX_COMP, FIT_MAX_COEF = 4, 512  # components and Fourier columns of one fit (fpta_batch_set_fit)
+OS_MAX_COMP, OS_MAX_COL, OS_MAX_COEF = 8, 1024, 512  # components, all Fourier columns, the target's (fpta_batch_set_os)
 ORF_PLAN_LEN = 10  # FPTA_ORF_PLAN_LEN
 ORF_PLAN_KEYS = ("tile", "chunk", "map_group", "n_tiles", "n_chunks", "n_split", "chunks_per_split", "n_groups",
                  "groups_per_launch", "workspace_bytes")
@@ -650,6 +657,132 @@ class Context:
                                                0.0 if rcond is None else float(rcond), n_vec, _ptr(res), _ptr(coef),
                                                _ptr(rank), _ptr(kept)), "fpta_fit_coefficients")
         return coef, rank, kept.astype(bool)
+
+    @staticmethod
+    def _os_args(what, P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G):
+        """The tables of an optimal-statistic call as contiguous arrays of the C types: the component tables as
+        _fit_args makes them (up to OS_MAX_COMP components, OS_MAX_COL columns), phi [P, sum N_c] (a row [sum N_c] is
+        repeated), masks None or uint8 [C, n] (an entry None: the component acts everywhere), phi_hat [N_target], G
+        [J, P, P]."""
+        n_modes = np.ascontiguousarray(n_modes, dtype=np.int32)
+        if n_modes.ndim != 1 or not 1 <= len(n_modes) <= OS_MAX_COMP or np.any(n_modes < 1):
+            raise ValueError(f"{what}: n_modes must hold 1 .. {OS_MAX_COMP} positive mode counts, got {n_modes}")
+        n_f = int(n_modes.sum())
+        if 2 * n_f > OS_MAX_COL:
+            raise ValueError(f"{what}: {2 * n_f} Fourier columns, more than {OS_MAX_COL}")
+        target = int(target)
+        if not 0 <= target < len(n_modes):
+            raise ValueError(f"{what}: target component {target} outside [0, {len(n_modes)})")
+        if 2 * int(n_modes[target]) > OS_MAX_COEF:
+            raise ValueError(f"{what}: the target has {2 * int(n_modes[target])} Fourier columns, more than "
+                             f"{OS_MAX_COEF}")
+        f = _f64(f)
+        if f.shape not in ((n_f,), (P, n_f)):
+            raise ValueError(f"{what}: f must be [{n_f}] or [{P}, {n_f}], got {f.shape}")
+        idx, freqf = _f64(idx), _f64(freqf)
+        if idx.shape != n_modes.shape or freqf.shape != n_modes.shape:
+            raise ValueError(f"{what}: idx and freqf must hold one value per component")
+        phi = _f64(phi)
+        if phi.shape == (n_f,):
+            phi = np.ascontiguousarray(np.tile(phi, (P, 1)))
+        if phi.shape != (P, n_f):
+            raise ValueError(f"{what}: phi must be [{n_f}] or [{P}, {n_f}], got {phi.shape}")
+        mask = None
+        if masks is not None and any(m is not None for m in masks):
+            if len(masks) != len(n_modes):
+                raise ValueError(f"{what}: {len(masks)} masks for {len(n_modes)} components")
+            mask = np.ones((len(n_modes), n), dtype=np.uint8)
+            for c, m in enumerate(masks):
+                if m is not None:
+                    m = np.asarray(m)
+                    if m.shape != (n,):
+                        raise ValueError(f"{what}: the mask of component {c} must hold {n} flags, got {m.shape}")
+                    mask[c] = m != 0
+        phi_hat = _f64(phi_hat)
+        if phi_hat.shape != (int(n_modes[target]),):
+            raise ValueError(f"{what}: the template must hold {int(n_modes[target])} values, got {phi_hat.shape}")
+        G = np.zeros((0, P, P)) if G is None else _f64(G)
+        if G.ndim == 2:
+            G = G[None]
+        if G.ndim != 3 or G.shape[1:] != (P, P):
+            raise ValueError(f"{what}: G must be [J, {P}, {P}], got {G.shape}")
+        return n_modes, f, idx, freqf, f.ndim == 1, phi, mask, target, phi_hat, np.ascontiguousarray(G)
+
+    def batch_set_os(self, n_modes, f, idx, freqf, phi, target, phi_hat, G, masks=None, M=None, ncol_psr=None,
+                     weights=None, rcond=None):
+        """The optimal statistic of the batch layout (fpta_batch_set_os): the noise model's components (n_modes, f, idx,
+        freqf as batch_set_fit; phi [P, sum N_c] or [sum N_c] prior variances; masks None or one entry per component),
+        the target component and its template phi_hat [N], the pair-weight matrices G [J, P, P], the marginalised
+        design M and the weights. n_modes None or empty clears it. Returns (kept columns of M [P], N_ab [P, P])."""
+        info = self.batch_info()
+        P, n = info["n_psr"], info["n_toa"]
+        rank = np.zeros(P, dtype=np.int32)
+        if P == 0 or n_modes is None or len(n_modes) == 0:  # without a layout: the library's own state error
+            self._check(_lib.fpta_batch_set_os(self._h, 0, None, None, 1, None, None, None, None, 0, None, 0, None,
+                                               None, None, 0.0, 0, None, _ptr(rank), None), "fpta_batch_set_os")
+            return rank, np.zeros((P, P))
+        n_modes, f, idx, freqf, common, phi, mask, target, phi_hat, G = self._os_args(
+            "batch_set_os", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G)
+        if M is None:
+            M = np.zeros((n, 0))
+        M, ncol_psr, weights = self._tm_args("batch_set_os", P, n, M, ncol_psr, weights)
+        nab = np.zeros((P, P))
+        self._check(_lib.fpta_batch_set_os(self._h, len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx),
+                                           _ptr(freqf), _ptr(phi), _ptr(mask), target, _ptr(phi_hat), M.shape[1],
+                                           _ptr(M), _ptr(ncol_psr), _ptr(weights),
+                                           0.0 if rcond is None else float(rcond), len(G), _ptr(G), _ptr(rank),
+                                           _ptr(nab)), "fpta_batch_set_os")
+        return rank, nab
+
+    def batch_os_info(self):
+        """K, N and J of the optimal statistic that is set (0: none) and the realizations of the last result
+        (fpta_batch_os_info)."""
+        info = np.zeros(4, dtype=np.int64)
+        self._check(_lib.fpta_batch_os_info(self._h, _ptr(info)), "fpta_batch_os_info")
+        return dict(K=int(info[0]), N=int(info[1]), J=int(info[2]), n_real=int(info[3]))
+
+    def batch_os(self, per_mode=False, coefficients=False):
+        """The optimal statistic of the last block (fpta_batch_os): (Q [J, R], Q_mode [J, N, R] or None, X [P, K, R] or
+        None). The buffers are sized from the library's own K, N and J."""
+        have = self.batch_os_info()
+        try:
+            _, _, R = self.batch_device_out()
+        except FptaError:
+            R = 0  # no block: the library's state error follows
+        Q = np.empty((have["J"], R))
+        Qm = np.empty((have["J"], have["N"], R)) if per_mode else None
+        X = np.empty((self.batch_info()["n_psr"], have["K"], R)) if coefficients else None
+        self._check(_lib.fpta_batch_os(self._h, _ptr(Q), _ptr(Qm), _ptr(X)), "fpta_batch_os")
+        return Q, Qm, X
+
+    def os_statistic(self, offs, toas, nu, n_modes, f, idx, freqf, phi, target, phi_hat, G, res, masks=None, M=None,
+                     ncol_psr=None, weights=None, rcond=None):
+        """The optimal statistic of every row of res [n_vec, n_toa] or [n_toa] for any array (fpta_os_statistic).
+        Returns (Q [J, n_vec], Q_mode [J, N, n_vec], X [P, K, n_vec], kept columns of M [P], N_ab [P, P])."""
+        offs = np.ascontiguousarray(offs, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1:
+            raise ValueError("os_statistic: offs must be [P + 1]")
+        P, n = len(offs) - 1, int(offs[-1])
+        toas, nu, res = _f64(toas), _f64(nu), _f64(res)
+        if toas.shape != (n,) or nu.shape != (n,):
+            raise ValueError(f"os_statistic: toas and nu must hold {n} values")
+        if res.ndim not in (1, 2) or res.shape[-1] != n:
+            raise ValueError(f"os_statistic: res must be [n_vec, {n}] or [{n}], got {res.shape}")
+        n_vec = 1 if res.ndim == 1 else res.shape[0]
+        n_modes, f, idx, freqf, common, phi, mask, target, phi_hat, G = self._os_args(
+            "os_statistic", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G)
+        if M is None:
+            M = np.zeros((n, 0))
+        M, ncol_psr, weights = self._tm_args("os_statistic", P, n, M, ncol_psr, weights)
+        N = int(n_modes[target])
+        Q, Qm, X = np.zeros((len(G), n_vec)), np.zeros((len(G), N, n_vec)), np.zeros((P, 2 * N, n_vec))
+        rank, nab = np.zeros(P, dtype=np.int32), np.zeros((P, P))
+        self._check(_lib.fpta_os_statistic(self._h, P, _ptr(offs), _ptr(toas), _ptr(nu), len(n_modes), _ptr(n_modes),
+                                           _ptr(f), int(common), _ptr(idx), _ptr(freqf), _ptr(phi), _ptr(mask), target,
+                                           _ptr(phi_hat), M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
+                                           0.0 if rcond is None else float(rcond), len(G), _ptr(G), n_vec, _ptr(res),
+                                           _ptr(Q), _ptr(Qm), _ptr(X), _ptr(rank), _ptr(nab)), "fpta_os_statistic")
+        return Q, Qm, X, rank, nab
 
     def batch_clear(self):
         self._check(_lib.fpta_batch_clear_signals(self._h), "fpta_batch_clear_signals")

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _capi
 from . import fit as _fit
+from . import os as _os
 from . import tm as _tm
 from fakepta.correlated_noises import orf_factor, orf_matrix
 
@@ -69,6 +70,7 @@ class BatchSimulator:
         self.ctx.batch_set_toas(self.offs, self.toas, self.freqs)
         self._has_tm = False  # set_timing_model
         self._fit = None  # set_fourier_fit: dict(n_modes, f, idx, freqf, common)
+        self._os = None  # set_optimal_statistic: dict(G, nab, n_orf, centres, counts, target, template)
         self.segments = []  # (name, kind, f, amp, idx, L, mask) — host copy for checking/reporting
         names = signals
         if names is None:
@@ -299,6 +301,52 @@ class BatchSimulator:
         _, _, R = self.ctx.batch_device_out()
         X = self.ctx.batch_fit_cross(int(fit["n_modes"].sum())) / R
         return X / (2.0 * _fit.mode_delta_f(fit["n_modes"], fit["f"]))[:, None, None] if psd else X
+
+    # ------------------------------------------------------------------ optimal statistic
+    def set_optimal_statistic(self, target=None, orfs=("hd",), bins=None, template=None, noise="layout", Mmats="tm",
+                              weights="white", rcond=None):
+        """Set the optimal statistic that optimal_statistic() applies to a block: per realization the noise-weighted
+        cross-correlation of every pulsar pair (X_a^T phi_hat X_b with X_p = F_p^T P_p^-1 r_p, the definition of
+        include/fakepta_amd.h) against the pair weights of ORFs and angular bins. Returns (kept design columns [P],
+        N_ab [P, P]).
+
+        target:   the common process: a signal name of the noise model or its index; None picks the layout's only
+                  common signal (ValueError with none or several).
+        orfs:     names fakepta's orf_matrix knows ("hd", "monopole", "dipole", "curn") or explicit [P, P] arrays.
+        bins:     None, or a number of angular bins (open, edges linspace(0, pi, bins + 1), as hd_curve).
+        template: phi_hat [N]; default the target's own amp^2, so A2 is in units of the injected power.
+        noise:    "layout": every signal of this layout (f, amp^2, idx, mask) makes P_p; or a list of such segments.
+        Mmats, weights, rcond: as set_fourier_fit; the design is marginalised with infinite variance, so project()
+                  before optimal_statistic() changes nothing but rounding.
+
+        The weights are diagonal: ECORR is not part of them."""
+        segs = self.segments if isinstance(noise, str) and noise == "layout" else noise
+        if isinstance(segs, str):
+            raise ValueError(f"set_optimal_statistic: noise must be 'layout' or a list of segments, got {noise!r}")
+        t = _os.pick_target(segs, target)
+        model = _os.noise_model(segs, len(self.psrs))
+        phi_hat = _os.template_of(model, t, template)
+        G, n_orf, centres, counts = _os.pair_matrices(self.psrs, orfs, bins)
+        M, ncol = _os.design_of(self.psrs, Mmats, "set_optimal_statistic")
+        w = _tm.weights_of(self.psrs, weights, self.n_toa)
+        self._os = None
+        rank, nab = self.ctx.batch_set_os(model["n_modes"], model["f"], model["idx"], model["freqf"], model["phi"], t,
+                                          phi_hat, G, masks=model["masks"], M=M, ncol_psr=ncol, weights=w, rcond=rcond)
+        self._os = dict(G=G, nab=nab, n_orf=n_orf, centres=centres, counts=counts, target=t, template=phi_hat)
+        return rank, nab
+
+    def optimal_statistic(self, per_mode=False):
+        """The optimal statistic of every realization of the last block, computed on the device; the block is
+        untouched. A dict: A2 and snr [n_orf, R] (each ORF on its own), A2_joint [n_orf, R] when more than one ORF is
+        set (the joint fit C A = Q), rho_bins [bins, R] with bin_centres and bin_counts (NaN for a bin without pairs),
+        Q [J, R] and norm [J] (the raw device numbers and their denominators, ORFs first, then bins), and Q_mode
+        [J, N, R] with per_mode=True. Per batch of a sharded job: simulate_sharded(..., on_batch=lambda sim, first, n:
+        ...sim.optimal_statistic()...)."""
+        if getattr(self, "_os", None) is None:
+            raise ValueError("optimal_statistic: no optimal statistic is set; call set_optimal_statistic() first")
+        o = self._os
+        Q, Qm, _ = self.ctx.batch_os(per_mode=per_mode)
+        return _os.derive(Q, o["G"], o["nab"], o["n_orf"], o["centres"], o["counts"], Qm)
 
     def synth_from_z(self, z):
         """Validation mode: z [n_real, n_seg, P, N_max, 2] standard normals (cos, sin)."""

@@ -1355,6 +1355,8 @@ int fpta_batch_set_toas(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const d
   c->has_tm = false;  // the timing model's tables are per TOA of the layout they were set for
   c->has_fit = false;  // and so are the Fourier fit's operators; its last result goes with them
   c->fit_R = 0;
+  c->has_os = false;  // the optimal statistic's operators too
+  c->os_R = 0;
   c->out_R = 0;
   return layout_set_toas(c, c->batch, n_psr, offs, toas, nu);
 }

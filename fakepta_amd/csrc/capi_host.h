@@ -212,6 +212,14 @@ struct fpta_ctx {
   DevBuf fit_a, fit_offs, fit_rank, fit_rows, fit_coef, fit_x, fit1_a, fit1_offs, fit1_rank, fit1_res, fit1_coef;
   bool has_fit = false, fit_common = false;
   int32_t fit_K = 0, fit_modes = 0, fit_R = 0, fit_rpad = 0;
+  // Optimal statistic (os.hip): k_fit_apply's second operator slot (pulsar p's B_p [K][n_p] at K offs[p], CSR offsets,
+  // the rows to make per pulsar) and coefficient buffer X [P][K][os_rpad], the template phi_hat [N], the J pair-weight
+  // matrices [J][P][P] and the results Q_mode [J][N][os_rpad], Q [J][os_rpad] of the last fpta_batch_os (os_R
+  // realizations; 0: none); the same tables plus the residuals of one fpta_os_statistic call
+  DevBuf os_a, os_offs, os_rows, os_coef, os_phi, os_g, os_qm, os_q;
+  DevBuf os1_a, os1_offs, os1_rows, os1_res, os1_coef, os1_phi, os1_g, os1_qm, os1_q;
+  bool has_os = false;
+  int32_t os_K = 0, os_N = 0, os_J = 0, os_R = 0, os_rpad = 0;
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
   int32_t out_R = 0;
@@ -427,6 +435,15 @@ int batch_common(fpta_ctx* c, uint64_t seed, int64_t real0, int32_t n_real, cons
                  double* out, double* coeffs_out, bool white);
 int launch_block_checksums(fpta_ctx* c, bool async = false, hipStream_t* used = nullptr, double* dst = nullptr,
                            bool* direct = nullptr);
+
+// fit.hip: k_fit_apply on any operator slot (coef [n_psr][K][R_pad] = A_p r, cleared first; rank[p] == 0: the pulsar
+// is skipped), and the download of such a buffer as [rows][R]. fit_launch books one FPTA_K_DENSE entry;
+// fit_launch_unbooked none (the caller's KTimer spans it).
+int fit_launch_unbooked(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K,
+                        const DevBuf& A, const DevBuf& offs, const DevBuf& rank, DevBuf& coef, int32_t& R_pad);
+int fit_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K, const DevBuf& A,
+               const DevBuf& offs, const DevBuf& rank, DevBuf& coef, int32_t& R_pad);
+int fit_download(fpta_ctx* c, const DevBuf& coef, int64_t rows, int32_t R, int32_t R_pad, double* host);
 
 // grid_host.hip
 constexpr double kGridAutoRatio = 0.5;  // auto path: gridded when it needs < half the direct FMAs

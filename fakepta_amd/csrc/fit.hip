@@ -226,9 +226,9 @@ __global__ __launch_bounds__(64) void k_fit_cross(CrossArgs a) {
   }
 }
 
-// Clears coef [n_psr][K][R_pad] and runs k_fit_apply on a block [R][ld] against device tables; one FPTA_K_DENSE entry
-static int fit_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K, const DevBuf& A,
-                      const DevBuf& offs, const DevBuf& rank, DevBuf& coef, int32_t& R_pad) {
+// Clears coef [n_psr][K][R_pad] and runs k_fit_apply on a block [R][ld] against device tables; no FPTA_K_DENSE entry
+int fit_launch_unbooked(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K,
+                        const DevBuf& A, const DevBuf& offs, const DevBuf& rank, DevBuf& coef, int32_t& R_pad) {
   R_pad = (R + kFitRpad - 1) / kFitRpad * kFitRpad;
   const size_t bytes = sizeof(double) * (size_t)n_psr * (size_t)K * (size_t)R_pad;
   if (coef.ensure(bytes) != hipSuccess)
@@ -246,7 +246,6 @@ static int fit_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int
   a.coef = coef.as<double>();
   const int64_t blocks = (int64_t)n_psr * a.n_rt;
   if (blocks > 0x7FFFFFFF) return fail(c, FPTA_EINVAL, "fit: too many pulsars x realization tiles");
-  KTimer kt(c, FPTA_K_DENSE);
   HIPCHK(c, hipMemsetAsync(coef.p, 0, bytes, c->stream), "fit coefficients clear");
   if (blocks == 0) return FPTA_OK;
   const dim3 grid((unsigned)blocks), block(64 * kFitWaves);
@@ -260,6 +259,18 @@ static int fit_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int
     k_fit_apply<1><<<grid, block, 0, c->stream>>>(a);
   HIPCHK(c, hipGetLastError(), "k_fit_apply launch");
   return FPTA_OK;
+}
+
+// The same with one FPTA_K_DENSE entry around the clear and the launch (the buffer is sized before the entry starts)
+int fit_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K, const DevBuf& A,
+               const DevBuf& offs, const DevBuf& rank, DevBuf& coef, int32_t& R_pad) {
+  const size_t bytes = sizeof(double) * (size_t)n_psr * (size_t)K * (size_t)((R + kFitRpad - 1) / kFitRpad * kFitRpad);
+  if (coef.ensure(bytes) != hipSuccess)
+    return fail(c, FPTA_ENOMEM, "fit: no device memory for " + std::to_string(bytes) + " bytes of coefficients");
+  if ((int64_t)n_psr * ((R + kFitReal - 1) / kFitReal) > 0x7FFFFFFF)
+    return fail(c, FPTA_EINVAL, "fit: too many pulsars x realization tiles");
+  KTimer kt(c, FPTA_K_DENSE);
+  return fit_launch_unbooked(c, res, ld, R, n_psr, K, A, offs, rank, coef, R_pad);
 }
 
 // Device copies of a plan's tables. The operator is the large one (8 K n_toa bytes): a failed allocation says so.
@@ -277,7 +288,7 @@ static int fit_upload(fpta_ctx* c, const fpta_fit::Plan& plan, int32_t n_psr, co
 }
 
 // coef [n_psr][K][R_pad] on the device -> host [n_psr][K][R]
-static int fit_download(fpta_ctx* c, const DevBuf& coef, int64_t rows, int32_t R, int32_t R_pad, double* host) {
+int fit_download(fpta_ctx* c, const DevBuf& coef, int64_t rows, int32_t R, int32_t R_pad, double* host) {
   if (rows > 0 && R > 0)
     HIPCHK(c, hipMemcpy2DAsync(host, sizeof(double) * (size_t)R, coef.p, sizeof(double) * (size_t)R_pad,
                                sizeof(double) * (size_t)R, (size_t)rows, hipMemcpyDeviceToHost, c->stream),

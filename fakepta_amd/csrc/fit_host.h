@@ -41,13 +41,13 @@ inline int64_t modes_of(const Spec& sp) {
 
 // Everything the entry points refuse beyond tm_host.h's validate (the pulsar table, the nuisance design, the
 // weights): the component list, the frequencies, the TOAs and the radio frequencies where a chromatic index needs
-// them. False with the reason in why.
+// them. False with the reason in why. max_comp and max_coef: the limits of the caller (os_host.h has wider ones).
 inline bool validate(int64_t n_psr, const int64_t* offs, const double* toas, const double* nu, const Spec& sp,
                      int64_t n_col, const double* M, const int32_t* ncol_psr, const double* weights,
-                     std::string& why) {
+                     std::string& why, int32_t max_comp = kMaxComp, int32_t max_coef = kMaxCoef) {
   if (!fpta_tm::validate(n_psr, offs, n_col, M, ncol_psr, weights, why)) return false;
-  if (sp.n_comp < 1 || sp.n_comp > kMaxComp) {
-    why = std::to_string(sp.n_comp) + " components outside [1, " + std::to_string(kMaxComp) + "]";
+  if (sp.n_comp < 1 || sp.n_comp > max_comp) {
+    why = std::to_string(sp.n_comp) + " components outside [1, " + std::to_string(max_comp) + "]";
     return false;
   }
   if (!sp.n_modes || !sp.f || !sp.idx || !sp.freqf) {
@@ -56,9 +56,9 @@ inline bool validate(int64_t n_psr, const int64_t* offs, const double* toas, con
   }
   int64_t n_f = 0;
   for (int32_t c = 0; c < sp.n_comp; ++c) {
-    if (sp.n_modes[c] < 1 || sp.n_modes[c] > kMaxCoef / 2) {
+    if (sp.n_modes[c] < 1 || sp.n_modes[c] > max_coef / 2) {
       why = "component " + std::to_string(c) + ": " + std::to_string(sp.n_modes[c]) + " modes outside [1, " +
-            std::to_string(kMaxCoef / 2) + "]";
+            std::to_string(max_coef / 2) + "]";
       return false;
     }
     n_f += sp.n_modes[c];
@@ -71,8 +71,8 @@ inline bool validate(int64_t n_psr, const int64_t* offs, const double* toas, con
       return false;
     }
   }
-  if (2 * n_f > kMaxCoef) {
-    why = std::to_string(2 * n_f) + " Fourier columns, more than " + std::to_string(kMaxCoef);
+  if (2 * n_f > max_coef) {
+    why = std::to_string(2 * n_f) + " Fourier columns, more than " + std::to_string(max_coef);
     return false;
   }
   const int64_t rows = sp.f_is_common ? 1 : n_psr;

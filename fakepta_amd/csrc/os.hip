@@ -1,0 +1,342 @@
+// Optimal statistic (fpta_batch_set_os, fpta_batch_os_info, fpta_batch_os, fpta_os_statistic): per realization the
+// noise-weighted cross-correlation of every pulsar pair against J pair-weight matrices. The definition is in
+// include/fakepta_amd.h; the per-pulsar operator B_p = F_p^T P_p^-1 and the pair normalisations are os_host.h's.
+//
+//   stage 1  X = B_p r of every realization: k_fit_apply (fit.hip) on this file's operator slot and coefficient buffer
+//            [P][K][R_pad]. The same instances as the Fourier fit, whose own slot is not touched.
+//   stage 2  k_os_pairs<JC>: Q_mode[j][m][r] = phi_hat_m sum_{a > b} G_j[a][b] (X_a,cos X_b,cos + X_a,sin X_b,sin). A
+//            workgroup of 4 waves owns 16 realizations of one mode and JC = 1, 2, 4 or 8 of the J matrices (the smallest
+//            that holds J, else slices of 8) and walks every lower 16 x 16 tile pair of pulsars. Per tile pair it stages
+//            the two X tiles [16 realizations][cos, sin][16 pulsars] and the JC G tiles (a <= b, pulsars past P and
+//            matrices past J as zeros) in LDS, from registers that were loaded during the previous pair's products; a
+//            wave then takes 4 realizations: one v_mfma_f64_16x16x4_f64 per realization makes the 256 pair products of
+//            the mode (k = cos, sin, 0, 0), and the lane contracts its four pairs (row (lane >> 4) + 4 q, column lane &
+//            15) with its four G values of each matrix. The pair products are made once and used for all JC matrices.
+//            Lane partials are kept over the tile pairs and summed over the 64 lanes by a butterfly at the end: a fixed
+//            order, no atomics, nothing shared between realizations, so a realization's Q is the same whatever R, its
+//            position and its neighbours; a matrix's sums are the same operations in every instance.
+//            k_os_reduce: Q[j][r] = sum_m Q_mode[j][m][r] in mode order.
+// Padding realizations have X = 0 (the cleared buffer) and give exact zeros; they are not downloaded.
+#include "capi_host.h"
+#include "os_host.h"
+#include "device_common.h"
+
+namespace __attribute__((visibility("hidden"))) capi {
+
+constexpr int kOsReal = 16;   // realizations of a workgroup
+constexpr int kOsWaves = 4;   // waves of a workgroup
+constexpr int kOsRW = kOsReal / kOsWaves;  // realizations of a wave
+constexpr int kOsJ = 8;       // pair-weight matrices of a workgroup, at most
+constexpr int kOsRpad = 32;   // k_fit_apply's realization padding: a multiple of kOsReal
+static_assert(kOsRpad % kOsReal == 0 && kOsReal == 16 && kOsWaves * 64 == 256,
+              "k_os_pairs stages 16 x 16 tiles with 256 threads and never reads past the padded realizations");
+
+struct OsArgs {
+  const double* X;    // [P][K][R_pad], K = 2 N: the cosine rows, then the sine rows
+  const double* phi;  // [N] the template
+  const double* G;    // [J][P][P] symmetric
+  double* Qm;         // [J][N][R_pad]
+  int32_t P, N, R_pad, J, n_tile;
+};
+
+// grid: (R_pad / 16, N, ceil(J / JC)); JC = 1, 2, 4, 8 matrices per workgroup (the smallest that holds J, else 8)
+template <int JC>
+__global__ __launch_bounds__(64 * kOsWaves) void k_os_pairs(OsArgs a) {
+  __shared__ double sX[2][kOsReal][2][16];  // [row tile, column tile][realization][cos, sin][pulsar]
+  __shared__ double sG[JC][4][64];          // [matrix][accumulator register][lane]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lg = lane >> 4;
+  const int r0 = (int)blockIdx.x * kOsReal, m = (int)blockIdx.y, j0 = (int)blockIdx.z * JC;
+  const int K = 2 * a.N;
+  const int s_rr = tid & 15, s_pi = tid >> 4;  // the X element this thread stages: realization, pulsar of the tile
+  FPTA_DCHECK(r0 + kOsReal <= a.R_pad, "k_os_pairs realization", r0 + kOsReal, a.R_pad + 1);
+  double part[JC][kOsRW];
+#pragma unroll
+  for (int jj = 0; jj < JC; ++jj)
+#pragma unroll
+    for (int rr = 0; rr < kOsRW; ++rr) part[jj][rr] = 0.0;
+
+  // this thread's share of a tile pair's operands: X of (row tile, column tile) x (cos, sin), and one G value per matrix
+  // (accumulator register q = wave of lane `lane`; a <= b, pulsars past P and matrices past J: zero)
+  auto fetch = [&](int ta, int tb, double (&xv)[4], double (&gv)[JC]) {
+#pragma unroll
+    for (int tile = 0; tile < 2; ++tile) {
+      const int p = (tile ? tb : ta) * 16 + s_pi;
+#pragma unroll
+      for (int cs = 0; cs < 2; ++cs) {
+        double v = 0.0;
+        if (p < a.P) v = a.X[((int64_t)p * K + cs * a.N + m) * a.R_pad + r0 + s_rr];
+        xv[2 * tile + cs] = v;
+      }
+    }
+    const int pa = ta * 16 + lg + 4 * wave, pb = tb * 16 + lr;
+    const bool in = pa < a.P && pb < pa;  // the strict lower triangle: a > b
+#pragma unroll
+    for (int jj = 0; jj < JC; ++jj) {
+      double v = 0.0;
+      if (in && j0 + jj < a.J) v = a.G[((int64_t)(j0 + jj) * a.P + pa) * a.P + pb];
+      gv[jj] = v;
+    }
+  };
+
+  double xv[4], gv[JC];
+  fetch(0, 0, xv, gv);
+  const int n_pairs = a.n_tile * (a.n_tile + 1) / 2;
+  for (int t = 0, ta = 0, tb = 0; t < n_pairs; ++t) {
+    __syncthreads();  // the previous tile pair's reads are done
+#pragma unroll
+    for (int tile = 0; tile < 2; ++tile)
+#pragma unroll
+      for (int cs = 0; cs < 2; ++cs) sX[tile][s_rr][cs][s_pi] = xv[2 * tile + cs];
+#pragma unroll
+    for (int jj = 0; jj < JC; ++jj) sG[jj][wave][lane] = gv[jj];
+    __syncthreads();
+    if (++tb > ta) {  // the next tile pair, row by row of the lower triangle
+      ++ta;
+      tb = 0;
+    }
+    if (t + 1 < n_pairs) fetch(ta, tb, xv, gv);  // in flight during this pair's products
+    d4 acc[kOsRW];
+#pragma unroll
+    for (int rr = 0; rr < kOsRW; ++rr) {
+      const int r = wave * kOsRW + rr;
+      const double av = lg < 2 ? sX[0][r][lg & 1][lr] : 0.0, bv = lg < 2 ? sX[1][r][lg & 1][lr] : 0.0;
+      acc[rr] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
+    }
+#pragma unroll
+    for (int jj = 0; jj < JC; ++jj) {
+      const double g0 = sG[jj][0][lane], g1 = sG[jj][1][lane], g2 = sG[jj][2][lane], g3 = sG[jj][3][lane];
+#pragma unroll
+      for (int rr = 0; rr < kOsRW; ++rr) {
+        double s = part[jj][rr];
+        s = fma(acc[rr][0], g0, s);
+        s = fma(acc[rr][1], g1, s);
+        s = fma(acc[rr][2], g2, s);
+        s = fma(acc[rr][3], g3, s);
+        part[jj][rr] = s;
+      }
+    }
+  }
+
+  const double ph = a.phi[m];
+#pragma unroll
+  for (int jj = 0; jj < JC; ++jj)
+#pragma unroll
+    for (int rr = 0; rr < kOsRW; ++rr) {
+      double s = part[jj][rr];
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+      if (lane == 0 && j0 + jj < a.J)
+        a.Qm[((int64_t)(j0 + jj) * a.N + m) * a.R_pad + r0 + wave * kOsRW + rr] = ph * s;
+    }
+}
+
+// Q[j][r] = sum_m Qm[j][m][r], in mode order; one thread per (j, r)
+__global__ __launch_bounds__(256) void k_os_reduce(const double* __restrict__ Qm, int32_t N, int32_t R_pad, int64_t n,
+                                                    double* __restrict__ Q) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const int64_t j = e / R_pad, r = e - j * R_pad;
+  double s = 0.0;
+  for (int32_t m = 0; m < N; ++m) s += Qm[(j * N + m) * R_pad + r];
+  Q[e] = s;
+}
+
+// One slot: the device tables of a statistic and its results
+struct OsSlot {
+  DevBuf &a, &offs, &rows, &coef, &phi, &g, &qm, &q;
+};
+
+static fpta_os::Spec os_spec(int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                             const double* idx, const double* freqf, const double* phi, const uint8_t* mask,
+                             int32_t target, const double* phi_hat) {
+  fpta_os::Spec sp;
+  sp.comps.n_comp = n_comp;
+  sp.comps.n_modes = n_modes;
+  sp.comps.f = f;
+  sp.comps.f_is_common = f_is_common != 0;
+  sp.comps.idx = idx;
+  sp.comps.freqf = freqf;
+  sp.phi = phi;
+  sp.mask = mask;
+  sp.target = target;
+  sp.phi_hat = phi_hat;
+  return sp;
+}
+
+// Device copies of a plan's tables, the template and the matrices. The operator is the large one (8 K n_toa bytes).
+static int os_upload(fpta_ctx* c, const fpta_os::Plan& plan, int32_t n_psr, const int64_t* offs, const double* phi_hat,
+                     int32_t n_g, const double* G, const OsSlot& s) {
+  const size_t bytes = sizeof(double) * plan.B.size();
+  if (s.a.ensure(bytes) != hipSuccess)
+    return fail(c, FPTA_ENOMEM, "os: no device memory for the operator of " + std::to_string(bytes) +
+                                    " bytes (8 K n_toa, K = " + std::to_string(plan.K) + ")");
+  int rc;
+  if ((rc = upload(c, s.a, plan.B.data(), bytes, "os operator"))) return rc;
+  if ((rc = upload(c, s.offs, offs, sizeof(int64_t) * ((size_t)n_psr + 1), "os offs"))) return rc;
+  if ((rc = upload(c, s.rows, plan.rows.data(), sizeof(int32_t) * (size_t)n_psr, "os rows"))) return rc;
+  if ((rc = upload(c, s.phi, phi_hat, sizeof(double) * (size_t)plan.N, "os template"))) return rc;
+  if ((rc = upload(c, s.g, G, sizeof(double) * (size_t)n_g * (size_t)n_psr * (size_t)n_psr, "os pair weights")))
+    return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream), "os upload sync");
+  return FPTA_OK;
+}
+
+// Both stages on a block [R][ld]; one FPTA_K_DENSE entry. The results stay in the slot: X [P][K][R_pad], Q_mode
+// [J][N][R_pad], Q [J][R_pad].
+static int os_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K, int32_t J,
+                     const OsSlot& s, int32_t& R_pad) {
+  R_pad = (R + kOsRpad - 1) / kOsRpad * kOsRpad;
+  const int32_t N = K / 2;
+  const size_t b_x = sizeof(double) * (size_t)n_psr * (size_t)K * (size_t)R_pad;
+  const size_t b_qm = sizeof(double) * (size_t)J * (size_t)N * (size_t)R_pad, b_q = sizeof(double) * (size_t)J * R_pad;
+  if (s.coef.ensure(b_x) != hipSuccess || s.qm.ensure(b_qm) != hipSuccess || s.q.ensure(b_q) != hipSuccess)
+    return fail(c, FPTA_ENOMEM, "os: no device memory for " + std::to_string(b_x + b_qm + b_q) + " bytes of results");
+  const int jc = J <= 1 ? 1 : J <= 2 ? 2 : J <= 4 ? 4 : kOsJ;  // matrices per workgroup
+  const int64_t n_jc = (J + jc - 1) / jc;
+  if (n_jc > 65535 || N > 65535) return fail(c, FPTA_EINVAL, "os: too many pair-weight matrices or modes");
+  KTimer kt(c, FPTA_K_DENSE);
+  int32_t rp = 0;
+  int rc = fit_launch_unbooked(c, res, ld, R, n_psr, K, s.a, s.offs, s.rows, s.coef, rp);
+  if (rc) return rc;
+  if (rp != R_pad) return fail(c, FPTA_EINVAL, "os: k_fit_apply's realization padding changed");
+  if (J == 0 || R == 0) return FPTA_OK;
+  OsArgs a;
+  a.X = s.coef.as<double>();
+  a.phi = s.phi.as<double>();
+  a.G = s.g.as<double>();
+  a.Qm = s.qm.as<double>();
+  a.P = n_psr;
+  a.N = N;
+  a.R_pad = R_pad;
+  a.J = J;
+  a.n_tile = (n_psr + 15) / 16;
+  const dim3 grid((unsigned)(R_pad / kOsReal), (unsigned)N, (unsigned)n_jc), block(64 * kOsWaves);
+  if (jc == 1)
+    k_os_pairs<1><<<grid, block, 0, c->stream>>>(a);
+  else if (jc == 2)
+    k_os_pairs<2><<<grid, block, 0, c->stream>>>(a);
+  else if (jc == 4)
+    k_os_pairs<4><<<grid, block, 0, c->stream>>>(a);
+  else
+    k_os_pairs<kOsJ><<<grid, block, 0, c->stream>>>(a);
+  HIPCHK(c, hipGetLastError(), "k_os_pairs launch");
+  const int64_t n = (int64_t)J * R_pad;
+  k_os_reduce<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(s.qm.as<double>(), N, R_pad, n,
+                                                                            s.q.as<double>());
+  HIPCHK(c, hipGetLastError(), "k_os_reduce launch");
+  return FPTA_OK;
+}
+
+static int os_results(fpta_ctx* c, const OsSlot& s, int32_t n_psr, int32_t K, int32_t J, int32_t R, int32_t R_pad,
+                      double* Q, double* Q_mode, double* X) {
+  int rc;
+  if (Q && J > 0 && (rc = fit_download(c, s.q, J, R, R_pad, Q))) return rc;
+  if (Q_mode && J > 0 && (rc = fit_download(c, s.qm, (int64_t)J * (K / 2), R, R_pad, Q_mode))) return rc;
+  if (X && (rc = fit_download(c, s.coef, (int64_t)n_psr * K, R, R_pad, X))) return rc;
+  return FPTA_OK;
+}
+
+}  // namespace capi
+
+using namespace capi;
+
+extern "C" int fpta_batch_set_os(fpta_ctx* c, int32_t n_comp, const int32_t* n_modes, const double* f,
+                                 int32_t f_is_common, const double* idx, const double* freqf, const double* phi,
+                                 const uint8_t* mask, int32_t target, const double* phi_hat, int32_t n_col,
+                                 const double* M, const int32_t* ncol_psr, const double* weights, double rcond,
+                                 int32_t n_g, const double* G, int32_t* rank_out, double* nab_out) {
+  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
+  const Layout& L = c->batch;
+  if (L.P <= 0) return fail(c, FPTA_ESTATE, "set_os: set_toas first");
+  if (n_comp == 0) {
+    c->has_os = false;
+    c->os_R = 0;
+    if (rank_out) std::fill(rank_out, rank_out + L.P, 0);
+    return FPTA_OK;
+  }
+  // everything is validated and the operators built here, before anything is uploaded
+  std::string why;
+  fpta_os::Plan plan;
+  const fpta_os::Spec sp = os_spec(n_comp, n_modes, f, f_is_common, idx, freqf, phi, mask, target, phi_hat);
+  const int made = fpta_os::make_plan(L.P, L.h_offs.data(), L.h_toas.data(), L.h_nu.data(), sp, n_col, M, ncol_psr,
+                                      weights, rcond, n_g, G, plan, why);
+  if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, "set_os: " + why);
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  c->has_os = false;
+  c->os_R = 0;
+  // a statistic with the previous operator may still read the tables
+  HIPCHK(c, hipStreamSynchronize(c->stream), "set_os sync");
+  const OsSlot s{c->os_a, c->os_offs, c->os_rows, c->os_coef, c->os_phi, c->os_g, c->os_qm, c->os_q};
+  int rc;
+  if ((rc = os_upload(c, plan, L.P, L.h_offs.data(), phi_hat, n_g, G, s))) return rc;
+  c->has_os = true;
+  c->os_K = plan.K;
+  c->os_N = plan.N;
+  c->os_J = n_g;
+  if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
+  if (nab_out) std::copy(plan.Nab.begin(), plan.Nab.end(), nab_out);
+  return FPTA_OK;
+}
+
+extern "C" int fpta_batch_os_info(fpta_ctx* c, int64_t* info) {
+  if (!c || !info) return fail(c, FPTA_EINVAL, "os_info: bad arguments");
+  info[0] = c->has_os ? c->os_K : 0;
+  info[1] = c->has_os ? c->os_N : 0;
+  info[2] = c->has_os ? c->os_J : 0;
+  info[3] = c->has_os ? c->os_R : 0;
+  return FPTA_OK;
+}
+
+extern "C" int fpta_batch_os(fpta_ctx* c, double* Q, double* Q_mode, double* X) {
+  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
+  if (!c->out_R) return fail(c, FPTA_ESTATE, "os: nothing synthesized yet");
+  if (!c->has_os) return fail(c, FPTA_ESTATE, "os: no optimal statistic is set (set_os first)");
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  int rc = join_red(c);  // a streamed job's reductions may still run beside the ctx stream
+  if (rc) return rc;
+  c->os_R = 0;
+  const OsSlot s{c->os_a, c->os_offs, c->os_rows, c->os_coef, c->os_phi, c->os_g, c->os_qm, c->os_q};
+  // the block is read only: part_ready and the next-block mix stay as they are
+  if ((rc = os_launch(c, c->out.as<double>(), c->out_ld, c->out_R, c->batch.P, c->os_K, c->os_J, s, c->os_rpad)))
+    return rc;
+  c->os_R = c->out_R;
+  return os_results(c, s, c->batch.P, c->os_K, c->os_J, c->os_R, c->os_rpad, Q, Q_mode, X);
+}
+
+extern "C" int fpta_os_statistic(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const double* toas, const double* nu,
+                                 int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                                 const double* idx, const double* freqf, const double* phi, const uint8_t* mask,
+                                 int32_t target, const double* phi_hat, int32_t n_col, const double* M,
+                                 const int32_t* ncol_psr, const double* weights, double rcond, int32_t n_g,
+                                 const double* G, int32_t n_vec, const double* res, double* Q, double* Q_mode,
+                                 double* X, int32_t* rank_out, double* nab_out) {
+  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
+  if (n_psr < 0 || n_vec < 0 || (n_psr > 0 && !offs)) return fail(c, FPTA_EINVAL, "os_statistic: bad arguments");
+  std::string why;
+  fpta_os::Plan plan;
+  const fpta_os::Spec sp = os_spec(n_comp, n_modes, f, f_is_common, idx, freqf, phi, mask, target, phi_hat);
+  const int made = fpta_os::make_plan(n_psr, offs, toas, nu, sp, n_col, M, ncol_psr, weights, rcond, n_g, G, plan, why);
+  if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, "os_statistic: " + why);
+  const int64_t n_toa = n_psr > 0 ? offs[n_psr] : 0;
+  if (n_vec > 0 && n_toa > 0 && !res) return fail(c, FPTA_EINVAL, "os_statistic: res missing");
+  if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
+  if (nab_out) std::copy(plan.Nab.begin(), plan.Nab.end(), nab_out);
+  if (n_vec == 0) return FPTA_OK;
+  if (n_psr == 0 || n_toa == 0) {  // nothing to launch: every X and every Q is zero
+    if (Q) std::fill(Q, Q + (int64_t)n_g * n_vec, 0.0);
+    if (Q_mode) std::fill(Q_mode, Q_mode + (int64_t)n_g * plan.N * n_vec, 0.0);
+    if (X) std::fill(X, X + (int64_t)n_psr * plan.K * n_vec, 0.0);
+    return FPTA_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  const OsSlot s{c->os1_a, c->os1_offs, c->os1_rows, c->os1_coef, c->os1_phi, c->os1_g, c->os1_qm, c->os1_q};
+  int rc;
+  if ((rc = os_upload(c, plan, n_psr, offs, phi_hat, n_g, G, s))) return rc;
+  if ((rc = upload(c, c->os1_res, res, sizeof(double) * (size_t)n_vec * (size_t)n_toa, "os_statistic residuals")))
+    return rc;
+  int32_t R_pad = 0;
+  if ((rc = os_launch(c, c->os1_res.as<double>(), n_toa, n_vec, n_psr, plan.K, n_g, s, R_pad))) return rc;
+  if ((rc = os_results(c, s, n_psr, plan.K, n_g, n_vec, R_pad, Q, Q_mode, X))) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream), "os_statistic sync");  // the residuals' upload is done with its source
+  return FPTA_OK;
+}

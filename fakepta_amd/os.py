@@ -1,0 +1,263 @@
+"""Optimal statistic: the noise-weighted cross-correlation statistic of every realization on the device
+(fpta_batch_set_os, fpta_batch_os, fpta_os_statistic; the definition is in include/fakepta_amd.h). The device returns
+one number per pair-weight matrix and realization, Q[j][r], and the host gets the pair normalisations N_ab with the
+plan. The helpers here are the host algebra around them: pair-weight matrices of named overlap reduction functions
+(ORFs) and angular bins, the noise model of a layout as the library's tables, and N_ab -> denominators, the joint fit of
+several ORFs and the binned correlations. BatchSimulator.set_optimal_statistic / optimal_statistic and the drop-in
+fake_pta.optimal_statistic_array share them. Nothing here needs a device except statistic_array's one call."""
+import numpy as np
+
+from . import _capi
+from . import tm as _tm
+
+MAX_COMP, MAX_COL, MAX_COEF = _capi.OS_MAX_COMP, _capi.OS_MAX_COL, _capi.OS_MAX_COEF
+
+
+def angular_bins(pos, bins):
+    """The pairs of every angular bin as pair-weight matrices: (G [bins, P, P] of 0 / 1, symmetric, zero diagonal; bin
+    centres; pairs per bin). Edges linspace(0, pi, bins + 1), open bins, as BatchSimulator.hd_curve: a pair exactly on
+    an edge is in no bin."""
+    bins = int(bins)
+    if bins < 1:
+        raise ValueError(f"bins must be a positive count, got {bins}")
+    pos = np.asarray(pos, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"pulsar positions must be [P, 3], got {pos.shape}")
+    P = len(pos)
+    ang = np.arccos(np.clip(pos @ pos.T, -1.0, 1.0))
+    edges = np.linspace(0.0, np.pi, bins + 1)
+    off = ~np.eye(P, dtype=bool)
+    G = np.stack([((ang > lo) & (ang < hi) & off).astype(np.float64) for lo, hi in zip(edges[:-1], edges[1:])])
+    G = np.maximum(G, G.transpose(0, 2, 1))  # arccos of a symmetric matrix is symmetric; make the flags exactly so
+    return G, edges[:-1] + 0.5 * (edges[1] - edges[0]), (G.sum(axis=(1, 2)) / 2).astype(np.int64)
+
+
+def check_pair_matrices(G, P):
+    """G as [J, P, P] float64: finite and exactly symmetric, else ValueError naming the matrix and the pair."""
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim == 2:
+        G = G[None]
+    if G.ndim != 3 or G.shape[1:] != (P, P):
+        raise ValueError(f"pair-weight matrices must be [J, {P}, {P}], got {G.shape}")
+    off = ~np.eye(P, dtype=bool)
+    for j, g in enumerate(G):
+        bad = np.argwhere(~np.isfinite(g) & off)
+        if len(bad):
+            raise ValueError(f"pair-weight matrix {j}, pair ({bad[0][0]}, {bad[0][1]}): not finite")
+        bad = np.argwhere(g != g.T)
+        if len(bad):
+            raise ValueError(f"pair-weight matrix {j}, pair ({bad[0][0]}, {bad[0][1]}): not symmetric")
+    return np.ascontiguousarray(G)
+
+
+def pair_matrices(psrs, orfs=("hd",), bins=None):
+    """(G [n_orf + bins, P, P], n_orf, bin centres, pairs per bin): one matrix per ORF (a name fakepta's orf_matrix
+    knows, or an explicit [P, P] array), then one per angular bin. The diagonal is ignored by the statistic and set to
+    zero here."""
+    from fakepta.correlated_noises import orf_matrix
+    P = len(psrs)
+    if isinstance(orfs, (str, np.ndarray)):
+        orfs = [orfs]
+    mats = []
+    for i, orf in enumerate(orfs):
+        if isinstance(orf, str):
+            g = np.array(orf_matrix(psrs, orf), dtype=np.float64)
+        else:
+            g = np.array(orf, dtype=np.float64)
+            if g.shape != (P, P):
+                raise ValueError(f"ORF {i} must be a name or a [{P}, {P}] array, got shape {g.shape}")
+        np.fill_diagonal(g, 0.0)
+        mats.append(g)
+    centres, counts = np.zeros(0), np.zeros(0, dtype=np.int64)
+    if bins is not None:
+        Gb, centres, counts = angular_bins(np.array([np.asarray(p.pos, dtype=np.float64) for p in psrs]), bins)
+        mats += list(Gb)
+    if not mats:
+        raise ValueError("the optimal statistic needs at least one ORF or angular bin")
+    return check_pair_matrices(np.stack(mats), P), len(orfs), centres, counts
+
+
+def _lower(P):
+    return np.tril_indices(P, -1)
+
+
+def norms(G, nab):
+    """[J]: sum_{a<b} G_j[a][b]^2 N_ab, the denominator of A2 (and, for a 0 / 1 matrix, of the binned rho)."""
+    il = _lower(nab.shape[0])
+    return np.array([np.sum(g[il] ** 2 * nab[il]) for g in G])
+
+
+def joint_matrix(G, nab):
+    """[J, J]: C_jj' = sum_{a<b} G_j[a][b] G_j'[a][b] N_ab, the normal matrix of the multi-ORF fit."""
+    il = _lower(nab.shape[0])
+    rows = np.array([g[il] for g in G])
+    return (rows * nab[il]) @ rows.T
+
+
+def derive(Q, G, nab, n_orf, centres=None, counts=None, Q_mode=None):
+    """Everything the host derives from Q [J, R] and N_ab: A2 and snr [n_orf, R], A2_joint [n_orf, R] for more than
+    one ORF (C A = Q), rho_bins [bins, R] (NaN for a bin without a pair of positive N_ab), bin_centres, bin_counts, Q,
+    norm [J] and, when given, Q_mode [J, N, R]."""
+    Q = np.asarray(Q, dtype=np.float64)
+    norm = norms(G, nab)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(norm[:, None] > 0, Q / norm[:, None], np.nan)
+        snr = np.where(norm[:n_orf, None] > 0, Q[:n_orf] / np.sqrt(norm[:n_orf, None]), np.nan)
+    out = dict(A2=ratio[:n_orf], snr=snr, rho_bins=ratio[n_orf:], Q=Q, norm=norm,
+               bin_centres=np.zeros(0) if centres is None else centres,
+               bin_counts=np.zeros(0, dtype=np.int64) if counts is None else counts)
+    if n_orf > 1:
+        out["A2_joint"] = np.linalg.solve(joint_matrix(G[:n_orf], nab), Q[:n_orf])
+    if Q_mode is not None:
+        out["Q_mode"] = Q_mode
+    return out
+
+
+def noise_model(segments, n_psr):
+    """BatchSimulator-style segments (dicts with name, kind 0 per-pulsar f, amp [P, N] / 1 common f, amp [N], idx,
+    freqf, mask) -> dict(names, n_modes [C] int32, f [sum N] or [P, sum N], idx, freqf, phi [P, sum N] = amp^2, masks).
+    One grid for the array when every segment is common, else per-pulsar rows."""
+    segments = list(segments)
+    if not 1 <= len(segments) <= MAX_COMP:
+        raise ValueError(f"the noise model takes 1 .. {MAX_COMP} components, got {len(segments)}")
+    per_psr = any(np.ndim(s["f"]) == 2 for s in segments)
+    fs, phis = [], []
+    for i, s in enumerate(segments):
+        f, amp = np.asarray(s["f"], dtype=np.float64), np.asarray(s["amp"], dtype=np.float64)
+        if f.shape != amp.shape or f.ndim not in (1, 2) or f.shape[-1] < 1 or (f.ndim == 2 and f.shape[0] != n_psr):
+            raise ValueError(f"component {i}: f and amp must both be [N] or [{n_psr}, N], got {f.shape} and "
+                             f"{amp.shape}")
+        if not np.all(np.isfinite(amp)):
+            raise ValueError(f"component {i}: an amplitude is not finite")
+        fs.append(np.tile(f, (n_psr, 1)) if per_psr and f.ndim == 1 else f)
+        phis.append(np.tile(amp ** 2, (n_psr, 1)) if amp.ndim == 1 else amp ** 2)
+    n_modes = np.array([f.shape[-1] for f in fs], dtype=np.int32)
+    if 2 * int(n_modes.sum()) > MAX_COL:
+        raise ValueError(f"{2 * int(n_modes.sum())} Fourier columns, more than {MAX_COL}")
+    return dict(names=[s.get("name") for s in segments], n_modes=n_modes,
+                f=np.ascontiguousarray(np.concatenate(fs, axis=-1)),
+                idx=np.array([float(s.get("idx", 0.0)) for s in segments]),
+                freqf=np.array([float(s.get("freqf", 1400.0)) for s in segments]),
+                phi=np.ascontiguousarray(np.concatenate(phis, axis=-1)), masks=[s.get("mask") for s in segments])
+
+
+def pick_target(segments, target=None):
+    """The index of the target component: a name, an index, or None for the only common (kind 1) segment."""
+    segments = list(segments)
+    if target is None:
+        common = [i for i, s in enumerate(segments) if s.get("kind") == 1]
+        if len(common) != 1:
+            raise ValueError(f"the layout has {len(common)} common signals: name the target of the optimal statistic")
+        return common[0]
+    if isinstance(target, str):
+        hit = [i for i, s in enumerate(segments) if s.get("name") == target]
+        if not hit:
+            raise KeyError(f"the noise model has no signal {target!r}")
+        return hit[0]
+    t = int(target)
+    if t != target or not 0 <= t < len(segments):
+        raise ValueError(f"target {target!r} is not a component index in [0, {len(segments)})")
+    return t
+
+
+def template_of(model, target, template=None):
+    """phi_hat [N]: the given template, or the target's own amp^2 (it is common, so every pulsar's row is the same and
+    A2 comes out in units of the injected power)."""
+    n0 = int(model["n_modes"][:target].sum())
+    N = int(model["n_modes"][target])
+    if template is None:
+        template = model["phi"][0, n0:n0 + N] if len(model["phi"]) else np.ones(N)
+    template = np.asarray(template, dtype=np.float64)
+    if template.shape != (N,):
+        raise ValueError(f"the template must hold the target's {N} modes, got shape {template.shape}")
+    if not np.all(np.isfinite(template) & (template > 0)):
+        raise ValueError("every template value must be positive and finite")
+    return template
+
+
+def segments_of(psrs, names=None):
+    """The noise model an array of Pulsar objects carries (signal_model and noisedict), as BatchSimulator lays it
+    out, without a device: per-pulsar signals on [P, N] grids (a pulsar without the signal, or with fewer modes, gets
+    zero amplitudes there), common signals on their own grid."""
+    from .batch import GP_NAMES, _df, _n_modes
+    P = len(psrs)
+    if names is None:
+        names = []
+        for p in psrs:
+            for s in p.signal_model:
+                if s not in names and (s in GP_NAMES or "common" in s or "system_noise" in s):
+                    names.append(s)
+    out = []
+    for name in names:
+        have = [p for p in psrs if name in p.signal_model]
+        if not have:
+            raise KeyError(f"no pulsar carries signal {name!r}")
+        sm0 = have[0].signal_model[name]
+        if "common" in name:
+            n = _n_modes(sm0)
+            f = np.asarray(sm0["f"], float)
+            out.append(dict(name=name, kind=1, f=f[:n], amp=np.sqrt(np.asarray(sm0["psd"], float) * _df(f))[:n],
+                            idx=float(sm0["idx"]), freqf=1400.0, mask=None))
+            continue
+        nm = max(_n_modes(p.signal_model[name]) for p in have)
+        f, amp = np.zeros((P, nm)), np.zeros((P, nm))
+        for i, p in enumerate(psrs):
+            if name in p.signal_model:
+                sm = p.signal_model[name]
+                n = _n_modes(sm)
+                fi = np.asarray(sm["f"], float)
+                amp[i, :n] = np.sqrt(np.asarray(sm["psd"], float) * _df(fi))[:n]
+                fi = fi[:n]
+                f[i, :n] = fi
+                if len(fi) < nm:
+                    step = fi[0] if len(fi) else 1.0
+                    f[i, len(fi):] = (fi[-1] if len(fi) else 0.0) + step * np.arange(1, nm - len(fi) + 1)
+            else:
+                f[i] = np.arange(1, nm + 1) / max(np.ptp(p.toas), 1.0)
+        idx, mask = float(sm0["idx"]), None
+        if "system_noise" in name:
+            backend = name.split("system_noise_")[1]
+            mask = np.concatenate([p.backend_flags == backend for p in psrs]).astype(np.uint8)
+            idx = 0.0
+        out.append(dict(name=name, kind=0, f=f, amp=amp, idx=idx, freqf=1400.0, mask=mask))
+    return out
+
+
+def design_of(psrs, Mmats, what):
+    """Mmats "tm" (each pulsar's Mmat), None (nothing marginalised) or a list of [n_p, m_p <= 16] -> (M, ncol_psr)."""
+    if isinstance(Mmats, str):
+        if Mmats != "tm":
+            raise ValueError(f"{what}: Mmats must be 'tm', None or a list of matrices, got {Mmats!r}")
+        Mmats = [p.Mmat for p in psrs]
+    if Mmats is None:
+        Mmats = [np.zeros((len(p.toas), 0)) for p in psrs]
+    Mmats = list(Mmats)
+    if len(Mmats) != len(psrs):
+        raise ValueError(f"{what}: {len(Mmats)} design matrices for {len(psrs)} pulsars")
+    for i, (m, p) in enumerate(zip(Mmats, psrs)):
+        if np.ndim(m) != 2 or np.shape(m)[0] != len(p.toas):
+            raise ValueError(f"{what}: design matrix of pulsar {i} must be [{len(p.toas)}, n_col], got shape "
+                             f"{np.shape(m)}")
+    return _tm.stack_design(Mmats)
+
+
+def statistic_array(psrs, target=None, orfs=("hd",), bins=None, template=None, signals=None, Mmats="tm",
+                    weights="white", rcond=None, per_mode=False, ctx=None):
+    """The optimal statistic of psr.residuals for a whole array in one device call (fpta_os_statistic): the dict of
+    derive() for one residual vector (R = 1). The noise model is what the pulsars carry: signal_model (every GP, or
+    `signals`) and the white noise of the noisedict as weights. ECORR is not part of the weights."""
+    segs = segments_of(psrs, signals)
+    t = pick_target(segs, target)
+    model = noise_model(segs, len(psrs))
+    phi_hat = template_of(model, t, template)
+    G, n_orf, centres, counts = pair_matrices(psrs, orfs, bins)
+    M, ncol = design_of(psrs, Mmats, "optimal_statistic_array")
+    offs = np.concatenate([[0], np.cumsum([len(p.toas) for p in psrs])]).astype(np.int64)
+    toas = np.concatenate([np.asarray(p.toas, dtype=np.float64) for p in psrs])
+    nu = np.concatenate([np.asarray(p.freqs, dtype=np.float64) for p in psrs])
+    res = np.concatenate([np.asarray(p.residuals, dtype=np.float64) for p in psrs])
+    ctx = ctx if ctx is not None else _capi.get_context()
+    Q, Qm, _, _, nab = ctx.os_statistic(offs, toas, nu, model["n_modes"], model["f"], model["idx"], model["freqf"],
+                                        model["phi"], t, phi_hat, G, res, masks=model["masks"], M=M, ncol_psr=ncol,
+                                        weights=_tm.weights_of(psrs, weights, int(offs[-1])), rcond=rcond)
+    return derive(Q, G, nab, n_orf, centres, counts, Qm if per_mode else None)

@@ -331,6 +331,78 @@ int fpta_fit_coefficients(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, con
                           double rcond, int32_t n_vec, const double* res /* [n_vec][n_toa_total] */,
                           double* coef_out /* [n_psr][K][n_vec] */, int32_t* rank_out, uint8_t* kept_out);
 
+/* ------------------------------------------------------------------ optimal statistic
+ * The noise-weighted optimal cross-correlation statistic of every realization of a block: per realization one number
+ * per pair-weight matrix, from which the host derives the amplitude estimate and S/N of an overlap reduction function
+ * (ORF), the joint fit of several ORFs and the binned pair correlations (added without a change of FPTA_VERSION: no
+ * existing call changes). This text is the specification.
+ * A "Fourier column" is (freqf / nu)^idx cos / sin(2 pi f_k t), cosines then sines, as in the Fourier fit above.
+ * Per pulsar p (n_p >= 0 TOAs): weights w > 0 (NULL: unit); a nuisance design M_p [n_p][m_p <= 16]; Gaussian-process
+ * components c = 0 .. C - 1, 1 <= C <= 8, with q = sum_c 2 N_c <= 1024 Fourier columns in all. Component c has
+ * frequencies (f [sum_c N_c] for the whole array, or [n_psr][sum_c N_c]), a chromatic index idx_c, a reference
+ * frequency freqf_c, an optional TOA mask (mask NULL, or [C][n_toa_total]: the component's columns are zero where its
+ * flag is 0; system noise) and prior variances phi [n_psr][sum_c N_c] >= 0 per pulsar and mode, the same for the
+ * cosine and the sine. A mode with phi = 0 is left out of the model for that pulsar.
+ * One component is the target (the common process): N modes, K = 2 N <= 512 columns F_p, and a template spectrum
+ * phi_hat [N] > 0. Its own phi stays part of P_p.
+ *   P_p = W^-1 + sum_c F_c Phi_c F_c^T + M_p inf M_p^T   (the timing model marginalised with infinite variance, so
+ *         whether the block was projected does not matter),
+ *   X_p = F_p^T P_p^-1 r_p  [K], one per realization,   Z_p = F_p^T P_p^-1 F_p  [K][K];
+ * a pulsar without TOAs has X = 0 and Z = 0. Per pair a < b: N_ab = tr(Z_a phi_hat Z_b phi_hat), phi_hat the diagonal
+ * over the K columns; rho_ab,r = X_a^T phi_hat X_b / N_ab; sigma_ab^2 = 1 / N_ab; a pair with N_ab = 0 has no rho and
+ * carries weight 0 everywhere. For J >= 0 symmetric pair-weight matrices G_j [n_psr][n_psr] (diagonal ignored) the one
+ * per-realization device quantity is
+ *   Q[j][m][r] = sum_{a<b} G_j[a][b] phi_hat_m (X_a,cos m,r X_b,cos m,r + X_a,sin m,r X_b,sin m,r),
+ *   Q[j][r] = sum_m Q[j][m][r], summed in mode order.
+ * The host derives the rest from Q and N_ab. A single ORF Gamma (G = Gamma): A2_r = Q_r / sum_{a<b} Gamma_ab^2 N_ab,
+ * S/N_r = Q_r / sqrt(sum_{a<b} Gamma_ab^2 N_ab). Several ORFs at once: C A_r = Q_.,r with C_jj' = sum_{a<b} Gamma^j_ab
+ * Gamma^j'_ab N_ab. Binned correlations (G = the indicator of the pairs of an angular bin): rho_bin,r = Q_r /
+ * sum_{pairs of the bin} N_ab.
+ * On the host, in long double, P_p and the normal equations are never formed: the columns of the stacked matrix
+ * [W^(1/2) T ; D^(1/2)], T = [M_p, the Fourier columns with phi > 0, the target's last], D = 0 on M_p's columns and
+ * 1 / phi on the others, are scaled to unit norm and orthogonalised in order by modified Gram-Schmidt, twice. M_p's
+ * columns follow the timing-model projection's rank rule (rcond; a dropped column is not marginalised); a Fourier
+ * column cannot drop. With the stacked Q = [Q1 ; Q2] and R, P^-1 T e_j = W^(1/2) Q1 R^-T e_j D_jj for a column of the
+ * model, without a subtraction; a target column with phi = 0 takes W^(1/2) (I - Q1 Q1^T) W^(1/2) F_k. B_p = F_p^T
+ * P_p^-1 [K][n_p] is rounded once to fp64 and uploaded (8 K n_toa_total bytes on the host and on the device; a failed
+ * allocation is FPTA_ENOMEM with the size in the message), Z_p = B_p F_p and N_ab stay on the host. The device
+ * computes X = B_p r with the Fourier fit's kernel (k_fit_apply) on an operator slot and a coefficient buffer of its
+ * own, so a Fourier fit and an optimal statistic can both be set, and Q on fp64 MFMA (k_os_pairs, k_os_reduce): the
+ * pair products of a realization are formed once and contracted with all J matrices, the strict lower triangle only,
+ * in a fixed order and without atomics. A realization's X and Q are bit-identical whatever the number of realizations,
+ * its position among them and its neighbours. The block is read only.
+ * Validated on the host before anything is uploaded or launched (FPTA_EINVAL; the message names the pulsar, component,
+ * mode or pair): everything the Fourier fit refuses (with C in [1, 8] and q <= 1024), a target index out of range,
+ * K > 512, a phi that is negative or not finite, a phi_hat that is not positive and finite, a G entry that is not
+ * finite, a G that is not symmetric (compared exactly). Kernel time is booked under FPTA_K_DENSE, one entry per call.
+ *
+ * fpta_batch_set_os: the statistic of the batch layout (after fpta_batch_set_toas, else FPTA_ESTATE). rank_out (NULL
+ *   or [n_psr]) gets the kept columns of M_p, nab_out (NULL or [n_psr][n_psr]) N_ab (symmetric, zero diagonal).
+ *   n_comp == 0 clears it, and so does fpta_batch_set_toas. Independent of fpta_batch_set_timing_model and
+ *   fpta_batch_set_fit.
+ * fpta_batch_os: the statistic of the context's last block on the context's stream (FPTA_ESTATE without a block or
+ *   without a statistic set). Q NULL or [J][n_real], Q_mode NULL or [J][N][n_real], X NULL or [n_psr][K][n_real].
+ * fpta_os_statistic: one call for any array and n_vec residual vectors res [n_vec][offs[n_psr]], independent of the
+ *   batch layout. A pulsar may have no TOAs. */
+int fpta_batch_set_os(fpta_ctx* ctx, int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                      const double* idx, const double* freqf, const double* phi /* [n_psr][sum_c N_c] */,
+                      const uint8_t* mask /* NULL or [n_comp][n_toa_total] */, int32_t target,
+                      const double* phi_hat /* [N_target] */, int32_t n_col,
+                      const double* M /* [n_toa_total][n_col] */, const int32_t* ncol_psr, const double* weights,
+                      double rcond, int32_t n_g, const double* G /* [n_g][n_psr][n_psr] */, int32_t* rank_out,
+                      double* nab_out);
+/* info[0] = K of the statistic that is set (0: none), info[1] = N, info[2] = J, info[3] = the realizations of the
+ * last fpta_batch_os result (0: none): what sizes Q, Q_mode and X. */
+int fpta_batch_os_info(fpta_ctx* ctx, int64_t* info /* [4] */);
+int fpta_batch_os(fpta_ctx* ctx, double* Q, double* Q_mode, double* X);
+int fpta_os_statistic(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const double* toas, const double* nu,
+                      int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                      const double* idx, const double* freqf, const double* phi, const uint8_t* mask, int32_t target,
+                      const double* phi_hat, int32_t n_col, const double* M, const int32_t* ncol_psr,
+                      const double* weights, double rcond, int32_t n_g, const double* G, int32_t n_vec,
+                      const double* res /* [n_vec][n_toa_total] */, double* Q, double* Q_mode, double* X,
+                      int32_t* rank_out, double* nab_out);
+
 /* Replaces fakepta/fake_pta.py:201-230 (add_white_noise), with ECORR fixed (defects D1/D2):
  *   residuals[t] += sigma[t] * z[t]  +  sum over blocks b containing t: ecorr_sigma[b] * zb[b]
  * Blocks are CSR: block_offs[n_blocks+1] into block_idx (TOA indices, any order).
@@ -657,7 +729,8 @@ int fpta_build_flags(void);
 #define FPTA_K_DENSE 4 /* dense covariance: basis + Gram, Cholesky, solves, draws; k_tm_project: one entry per call
                         * (fpta_batch_project, fpta_tm_project); k_fit_apply and k_fit_cross: one entry per call
                         * (fpta_batch_fit, fpta_fit_coefficients, fpta_batch_fit_cross); fpta_orf_anisotropic: one entry per
-                          launch batch (k_orf_aniso + k_orf_reduce) */
+                          launch batch (k_orf_aniso + k_orf_reduce); fpta_batch_os, fpta_os_statistic: one entry per
+                          call (k_fit_apply + k_os_pairs + k_os_reduce) */
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
 #define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]);
                         * fpta_batch_cw_accumulate: one entry per call (k_cw_block, or those kernels + k_cw_bcast) */
