@@ -88,6 +88,7 @@ _SIGS = [
     ("fpta_debug_normals", _c_int, [_ctx_p, _i64, _vp, _vp]),
     ("fpta_debug_fill_out", _c_int, [_ctx_p, _dbl]),
     ("fpta_debug_fused_shape", _c_int, [_ctx_p, _vp]),
+    ("fpta_debug_dense", _c_int, [_ctx_p, _i32, _i64, _i64, _vp]),
     ("fpta_get_option", _c_int, [_ctx_p, _i32, ctypes.POINTER(_i64)]),
     ("fpta_build_flags", _c_int, []),
     ("fpta_batch_path_reason", ctypes.c_char_p, [_ctx_p]),
@@ -113,7 +114,7 @@ _SIGS = [
 ]
 # entry points newer than an older library a same-box A/B may load through FAKEPTA_AMD_LIB (tools/gpu_ab_cfg.sh LIB=):
 # bound when present (the product library exports every one: tests/test_capi_symbols.py)
-_OPTIONAL = {"fpta_debug_normals", "fpta_debug_fused_shape"}
+_OPTIONAL = {"fpta_debug_normals", "fpta_debug_fused_shape", "fpta_debug_dense"}
 for _name, _res, _args in _SIGS:
     try:
         _fn = getattr(_lib, _name)
@@ -296,6 +297,7 @@ class Context:
         n, keep, args = self._dense_args(toas, nu, segments, white_var)
         cov = np.empty((n, n), dtype=np.float64)
         self._check(_lib.fpta_gp_covariance(self._h, *args, _ptr(cov)), "fpta_gp_covariance")
+        self._dense_shape = (n, 0)
         del keep
         return cov
 
@@ -306,6 +308,7 @@ class Context:
         assert len(r) == n
         out = np.empty(n, dtype=np.float64)
         self._check(_lib.fpta_noise_wiener(self._h, *args, _ptr(r), _ptr(out)), "fpta_noise_wiener")
+        self._dense_shape = (n, 0)
         del keep
         return out
 
@@ -315,8 +318,19 @@ class Context:
         out = np.empty((n_real, n), dtype=np.float64)
         self._check(_lib.fpta_noise_draw(self._h, *args, int(seed) & 0xFFFFFFFFFFFFFFFF, int(real0), int(n_real),
                                          _ptr(out)), "fpta_noise_draw")
+        self._dense_shape = (n, int(n_real))
         del keep
         return out
+
+    def debug_dense(self, what):
+        """What the last dense call of this context left on the device (fpta_debug_dense): what = 0 the matrix [n, n]
+        (after noise_wiener / noise_draw the Cholesky factor in its lower triangle), 1 the solve's y [n] (after
+        noise_wiener), 2 the normals [n, n_real] of the last noise_draw. FptaError when that call left no such item."""
+        n, n_real = getattr(self, "_dense_shape", (0, 0))
+        rows, cols = n, {0: n, 1: 1, 2: n_real}.get(int(what), 0)
+        out = np.empty((rows, cols) if rows * cols else (1, 1), dtype=np.float64)  # empty: the library refuses
+        self._check(_lib.fpta_debug_dense(self._h, int(what), rows, cols, _ptr(out)), "fpta_debug_dense")
+        return out[:, 0].copy() if what == 1 else out
 
     def gp_accumulate_array(self, offs, toas, nu, segments, residuals, sign=1.0, masks=None):
         """Array form: segments = list of (f [P, N], ccos [P, N], csin [P, N], idx, freqf);

@@ -756,6 +756,7 @@ int dense_build(fpta_ctx* c, int64_t n, const double* toas, const double* nu, in
                 const double* seg_freqf, const double* white_var, DenseDims& d) {
   if (n <= 0 || !toas || !nu || n_seg <= 0 || !seg_nmodes || !f || !w || !seg_idx || !seg_freqf)
     return fail(c, FPTA_EINVAL, "dense: bad arguments");
+  c->dn_last.stage = 0;  // the buffers are about to change; the calling entry point records what it leaves
   if (n > (int64_t)1 << 17) return fail(c, FPTA_EINVAL, "dense: more than 131072 TOAs");
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   int64_t M = 0;
@@ -800,6 +801,13 @@ int dense_build(fpta_ctx* c, int64_t n, const double* toas, const double* nu, in
                         white_var ? c->dn_white.as<double>() : nullptr),
          "k_gemm_tn (gram) launch");
   return FPTA_OK;
+}
+
+// What a completed dense call left on the device, for fpta_debug_dense (stage: 1 covariance, 2 factor + solve,
+// 3 factor + draws).
+void dense_remember(fpta_ctx* c, const DenseDims& d, int stage, int64_t ldz = 0, int32_t n_real = 0) {
+  c->dn_last.n = d.n, c->dn_last.n_pad = d.n_pad, c->dn_last.n_modes = d.n_modes, c->dn_last.k_pad = d.k_pad;
+  c->dn_last.ldz = ldz, c->dn_last.n_real = n_real, c->dn_last.stage = stage;
 }
 
 // In-place lower Cholesky of C (right-looking, 64-wide panels: diagonal block in LDS, panel solve,
@@ -1287,6 +1295,7 @@ int fpta_gp_covariance(fpta_ctx* c, int64_t n_toa, const double* toas, const dou
                           n_toa, hipMemcpyDeviceToHost, c->stream),
          "gp_covariance download");
   HIPCHK(c, hipStreamSynchronize(c->stream), "gp_covariance sync");
+  dense_remember(c, d, 1);
   return FPTA_OK;
 }
 
@@ -1312,6 +1321,7 @@ int fpta_noise_wiener(fpta_ctx* c, int64_t n_toa, const double* toas, const doub
   HIPCHK(c, hipMemcpyAsync(out, c->dn_out.p, sizeof(double) * n_toa, hipMemcpyDeviceToHost, c->stream),
          "noise_wiener download");
   HIPCHK(c, hipStreamSynchronize(c->stream), "noise_wiener sync");
+  dense_remember(c, d, 2);
   return FPTA_OK;
 }
 
@@ -1345,6 +1355,7 @@ int fpta_noise_draw(fpta_ctx* c, int64_t n_toa, const double* toas, const double
                            c->stream),
          "noise_draw download");
   HIPCHK(c, hipStreamSynchronize(c->stream), "noise_draw sync");
+  dense_remember(c, d, 3, ldz, n_real);
   return FPTA_OK;
 }
 
@@ -1728,6 +1739,31 @@ int fpta_debug_normals(fpta_ctx* c, int64_t n, const uint32_t* words, double* ou
   HIPCHK(c, hipMemcpyAsync(out, c->dbg_b.p, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, c->stream),
          "normals download");
   HIPCHK(c, hipStreamSynchronize(c->stream), "normals sync");
+  return FPTA_OK;
+}
+
+int fpta_debug_dense(fpta_ctx* c, int32_t what, int64_t rows, int64_t cols, double* out) {
+  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
+  if (!out || what < 0 || what > 2) return fail(c, FPTA_EINVAL, "debug_dense: bad arguments");
+  const fpta_ctx::DenseLast& l = c->dn_last;
+  if (!l.stage) return fail(c, FPTA_ESTATE, "debug_dense: no dense call has completed on this context");
+  if (what == 1 && l.stage != 2)
+    return fail(c, FPTA_ESTATE, "debug_dense: the last dense call was not fpta_noise_wiener");
+  if (what == 2 && l.stage != 3)
+    return fail(c, FPTA_ESTATE, "debug_dense: the last dense call was not fpta_noise_draw");
+  const int64_t want_cols = what == 0 ? l.n : what == 1 ? 1 : l.n_real;
+  if (rows != l.n || cols != want_cols)
+    return fail(c, FPTA_ESTATE,
+                "debug_dense: the last dense call left " + std::to_string(l.n) + " x " + std::to_string(want_cols) +
+                    ", not " + std::to_string(rows) + " x " + std::to_string(cols));
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  const void* src = what == 0 ? c->dn_C.p : what == 1 ? c->dn_y.p : c->dn_Z.p;
+  const size_t pitch = sizeof(double) * (size_t)(what == 0 ? l.n_pad : what == 1 ? 1 : l.ldz);
+  HIPCHK(c,
+         hipMemcpy2DAsync(out, sizeof(double) * (size_t)cols, src, pitch, sizeof(double) * (size_t)cols, (size_t)rows,
+                          hipMemcpyDeviceToHost, c->stream),
+         "debug_dense download");
+  HIPCHK(c, hipStreamSynchronize(c->stream), "debug_dense sync");
   return FPTA_OK;
 }
 

@@ -356,6 +356,14 @@ struct fpta_ctx {
   // dense-covariance path: inputs, basis G^T [k_pad][n_pad], matrix C [n_pad][n_pad], panel, draws
   DevBuf dn_toas, dn_nu, dn_f, dn_sw, dn_segof, dn_segidx, dn_segff, dn_white, dn_GT, dn_C, dn_PT, dn_info, dn_r,
       dn_y, dn_out, dn_Z;
+  // what the last dense call left in those buffers (fpta_debug_dense): its extents, the normals' leading dimension
+  // and draw count, and the stage it reached (0 nothing or a failed call, 1 covariance, 2 factor + solve, 3 factor +
+  // draws)
+  struct DenseLast {
+    int64_t n = 0, n_pad = 0, ldz = 0;
+    int32_t n_modes = 0, k_pad = 0, n_real = 0;
+    int stage = 0;
+  } dn_last;
 };
 
 namespace __attribute__((visibility("hidden"))) capi {  // library-internal: not exported

@@ -755,6 +755,14 @@ int fpta_debug_fill_out(fpta_ctx* ctx, double value);
  * (1: grid signal 0 = a per-pulsar + a common member and signal 1 = a per-pulsar member; 2: one grid signal of one
  * common member); 0, the general instance; -1, the block ran no k_grid_fused. Additive (tests). */
 int fpta_debug_fused_shape(fpta_ctx* ctx, int32_t* shape);
+/* The intermediates the last dense call (fpta_gp_covariance / fpta_noise_wiener / fpta_noise_draw) of this context
+ * left on the device, row-major into out [rows][cols], n = that call's n_toa: what = 0 the matrix [n][n] as it stands
+ * (the covariance after fpta_gp_covariance; after the other two the Cholesky factor in the lower triangle, zeros above
+ * the diagonal inside each 64 x 64 diagonal block and the covariance's untouched upper blocks elsewhere); what = 1
+ * the solve's y = C^-1 residuals [n][1], after fpta_noise_wiener only; what = 2 the normals [n][n_real] (TOA-major)
+ * of the last fpta_noise_draw. FPTA_ESTATE when the last dense call failed, did not produce the item, or left other
+ * extents than rows x cols. Additive (tests). */
+int fpta_debug_dense(fpta_ctx* ctx, int32_t what, int64_t rows, int64_t cols, double* out);
 
 #ifdef __cplusplus
 }
