@@ -556,6 +556,20 @@ def optimal_statistic_array(psrs, target=None, orfs=('hd',), bins=None, template
                                per_mode=per_mode)
 
 
+def likelihood_grid_array(psrs, target=None, phi=None, log10_A=None, gamma=None, signals=None, marginalize_tm=True,
+                          weights='white', rcond=None, per_pulsar=False, posterior=False):
+    """The Gaussian log-likelihood ratio of psr.residuals on a grid of spectra of the target process, for a whole array
+    in ONE GPU call (not in the reference): dlnL[g] = ln p(r | phi_g) - ln p(r | phi = 0) with the timing model
+    marginalised. The noise model is what the pulsars carry, as optimal_statistic_array takes it; the target's own
+    spectrum is replaced by the grid: either phi [G, N] (prior variance per mode) or the axes log10_A and gamma of a
+    power-law grid. Returns a dict: dlnL, argmax, lnB, the axes and on request the posterior and the per-pulsar terms
+    (fakepta_amd.lnl.derive, R = 1). ECORR is not part of the weights. residuals and signal_model are untouched."""
+    from fakepta_amd import lnl as _lnl
+    return _lnl.grid_array(psrs, target=target, phi=phi, log10_A=log10_A, gamma=gamma, signals=signals,
+                           Mmats='tm' if marginalize_tm else None, weights=weights, rcond=rcond,
+                           per_pulsar=per_pulsar, want_posterior=posterior)
+
+
 def fit_timing_model_array(psrs, weights='white', rcond=None):
     """Pulsar.fit_timing_model for a whole array in ONE GPU call. weights: 'white', None, an array over all TOAs or a
     list of per-pulsar arrays. Returns the ranks [P]."""

@@ -61,6 +61,12 @@ _SIGS = [
     ("fpta_batch_os", _c_int, [_ctx_p, _vp, _vp, _vp]),
     ("fpta_os_statistic", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
                                    _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fpta_batch_set_lnl", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _dbl,
+                                    _i32, _vp, _vp, _vp]),
+    ("fpta_batch_lnl_info", _c_int, [_ctx_p, _vp]),
+    ("fpta_batch_lnl", _c_int, [_ctx_p, _vp, _vp, _vp]),
+    ("fpta_lnl_grid", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp,
+                               _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_white_accumulate", _c_int, [_ctx_p, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_gp_covariance", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_noise_wiener", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -146,6 +152,7 @@ EPHEM_MSUN = 1.327124400e20 / 6.6743e-11  # FPTA_EPHEM_MSUN
 TM_MAX_COL = 16  # columns of one pulsar's design matrix (fpta_tm_project, fpta_batch_set_timing_model)
 FIT_MAX_COMP, FIT_MAX_COEF = 4, 512  # components and Fourier columns of one fit (fpta_batch_set_fit)
 OS_MAX_COMP, OS_MAX_COL, OS_MAX_COEF = 8, 1024, 512  # components, all Fourier columns, the target's (fpta_batch_set_os)
+LNL_MAX_COEF, LNL_MAX_GRID = 256, 4096  # the target's Fourier columns and the grid points (fpta_batch_set_lnl)
 ORF_PLAN_LEN = 10  # FPTA_ORF_PLAN_LEN
 ORF_PLAN_KEYS = ("tile", "chunk", "map_group", "n_tiles", "n_chunks", "n_split", "chunks_per_split", "n_groups",
                  "groups_per_launch", "workspace_bytes")
@@ -797,6 +804,103 @@ class Context:
                                            0.0 if rcond is None else float(rcond), len(G), _ptr(G), n_vec, _ptr(res),
                                            _ptr(Q), _ptr(Qm), _ptr(X), _ptr(rank), _ptr(nab)), "fpta_os_statistic")
         return Q, Qm, X, rank, nab
+
+    @classmethod
+    def _lnl_args(cls, what, P, n, n_modes, f, idx, freqf, phi, masks, target, phi_grid):
+        """The tables of a likelihood-grid call: _os_args' (without a template and pair weights) and phi_grid [G, N]
+        (a row [N] is one grid point) within the library's limits."""
+        n_modes = np.ascontiguousarray(n_modes, dtype=np.int32)
+        t = int(target)
+        N = int(n_modes[t]) if n_modes.ndim == 1 and 0 <= t < len(n_modes) else 1
+        n_modes, f, idx, freqf, common, phi, mask, target, _, _ = cls._os_args(
+            what, P, n, n_modes, f, idx, freqf, phi, masks, target, np.ones(N), None)
+        if 2 * N > LNL_MAX_COEF:
+            raise ValueError(f"{what}: the target has {2 * N} Fourier columns, more than {LNL_MAX_COEF}")
+        phi_grid = _f64(phi_grid)
+        if phi_grid.ndim == 1:
+            phi_grid = phi_grid[None]
+        if phi_grid.ndim != 2 or phi_grid.shape[1] != N:
+            raise ValueError(f"{what}: the grid must be [G, {N}], got {phi_grid.shape}")
+        if not 1 <= len(phi_grid) <= LNL_MAX_GRID:
+            raise ValueError(f"{what}: {len(phi_grid)} grid points outside [1, {LNL_MAX_GRID}]")
+        return n_modes, f, idx, freqf, common, phi, mask, target, np.ascontiguousarray(phi_grid)
+
+    def batch_set_lnl(self, n_modes, f, idx, freqf, phi, target, phi_grid, masks=None, M=None, ncol_psr=None,
+                      weights=None, rcond=None):
+        """The likelihood grid of the batch layout (fpta_batch_set_lnl): the noise model as batch_set_os takes it, the
+        target component (its own phi is not part of the base model) and phi_grid [G, N], the target's prior variance
+        per grid point and mode. n_modes None or empty clears it. Returns (kept columns of M [P], ld [P, G])."""
+        info = self.batch_info()
+        P, n = info["n_psr"], info["n_toa"]
+        rank = np.zeros(P, dtype=np.int32)
+        if P == 0 or n_modes is None or len(n_modes) == 0:  # without a layout: the library's own state error
+            self._check(_lib.fpta_batch_set_lnl(self._h, 0, None, None, 1, None, None, None, None, 0, 0, None, None,
+                                                None, 0.0, 0, None, _ptr(rank), None), "fpta_batch_set_lnl")
+            return rank, np.zeros((P, 0))
+        n_modes, f, idx, freqf, common, phi, mask, target, phi_grid = self._lnl_args(
+            "batch_set_lnl", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_grid)
+        if M is None:
+            M = np.zeros((n, 0))
+        M, ncol_psr, weights = self._tm_args("batch_set_lnl", P, n, M, ncol_psr, weights)
+        ld = np.zeros((P, len(phi_grid)))
+        self._check(_lib.fpta_batch_set_lnl(self._h, len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx),
+                                            _ptr(freqf), _ptr(phi), _ptr(mask), target, M.shape[1], _ptr(M),
+                                            _ptr(ncol_psr), _ptr(weights), 0.0 if rcond is None else float(rcond),
+                                            len(phi_grid), _ptr(phi_grid), _ptr(rank), _ptr(ld)), "fpta_batch_set_lnl")
+        return rank, ld
+
+    def batch_lnl_info(self):
+        """K, N and G of the likelihood grid that is set (0: none) and the realizations of the last result
+        (fpta_batch_lnl_info)."""
+        info = np.zeros(4, dtype=np.int64)
+        self._check(_lib.fpta_batch_lnl_info(self._h, _ptr(info)), "fpta_batch_lnl_info")
+        return dict(K=int(info[0]), N=int(info[1]), G=int(info[2]), n_real=int(info[3]))
+
+    def batch_lnl(self, per_pulsar=False, coefficients=False):
+        """The likelihood grid of the last block (fpta_batch_lnl): (dlnL [G, R], q_psr [P, G, R] or None, X [P, K, R] or
+        None). The buffers are sized from the library's own K and G."""
+        have = self.batch_lnl_info()
+        try:
+            _, _, R = self.batch_device_out()
+        except FptaError:
+            R = 0  # no block: the library's state error follows
+        P = self.batch_info()["n_psr"]
+        d = np.empty((have["G"], R))
+        q = np.empty((P, have["G"], R)) if per_pulsar else None
+        X = np.empty((P, have["K"], R)) if coefficients else None
+        self._check(_lib.fpta_batch_lnl(self._h, _ptr(d), _ptr(q), _ptr(X)), "fpta_batch_lnl")
+        return d, q, X
+
+    def lnl_grid(self, offs, toas, nu, n_modes, f, idx, freqf, phi, target, phi_grid, res, masks=None, M=None,
+                 ncol_psr=None, weights=None, rcond=None, factors=False):
+        """The likelihood grid of every row of res [n_vec, n_toa] or [n_toa] for any array (fpta_lnl_grid). Returns
+        (dlnL [G, n_vec], q_psr [P, G, n_vec], X [P, K, n_vec], kept columns of M [P], ld [P, G], U [P, G, K, K] (the
+        plan's fp64 factors) or None)."""
+        offs = np.ascontiguousarray(offs, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1:
+            raise ValueError("lnl_grid: offs must be [P + 1]")
+        P, n = len(offs) - 1, int(offs[-1])
+        toas, nu, res = _f64(toas), _f64(nu), _f64(res)
+        if toas.shape != (n,) or nu.shape != (n,):
+            raise ValueError(f"lnl_grid: toas and nu must hold {n} values")
+        if res.ndim not in (1, 2) or res.shape[-1] != n:
+            raise ValueError(f"lnl_grid: res must be [n_vec, {n}] or [{n}], got {res.shape}")
+        n_vec = 1 if res.ndim == 1 else res.shape[0]
+        n_modes, f, idx, freqf, common, phi, mask, target, phi_grid = self._lnl_args(
+            "lnl_grid", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_grid)
+        if M is None:
+            M = np.zeros((n, 0))
+        M, ncol_psr, weights = self._tm_args("lnl_grid", P, n, M, ncol_psr, weights)
+        K, G = 2 * int(n_modes[target]), len(phi_grid)
+        d, q, X = np.zeros((G, n_vec)), np.zeros((P, G, n_vec)), np.zeros((P, K, n_vec))
+        rank, ld = np.zeros(P, dtype=np.int32), np.zeros((P, G))
+        U = np.zeros((P, G, K, K)) if factors else None
+        self._check(_lib.fpta_lnl_grid(self._h, P, _ptr(offs), _ptr(toas), _ptr(nu), len(n_modes), _ptr(n_modes),
+                                       _ptr(f), int(common), _ptr(idx), _ptr(freqf), _ptr(phi), _ptr(mask), target,
+                                       M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
+                                       0.0 if rcond is None else float(rcond), G, _ptr(phi_grid), n_vec, _ptr(res),
+                                       _ptr(d), _ptr(q), _ptr(X), _ptr(rank), _ptr(ld), _ptr(U)), "fpta_lnl_grid")
+        return d, q, X, rank, ld, U
 
     def batch_clear(self):
         self._check(_lib.fpta_batch_clear_signals(self._h), "fpta_batch_clear_signals")

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _capi
 from . import fit as _fit
+from . import lnl as _lnl
 from . import os as _os
 from . import tm as _tm
 from fakepta.correlated_noises import orf_factor, orf_matrix
@@ -71,6 +72,7 @@ class BatchSimulator:
         self._has_tm = False  # set_timing_model
         self._fit = None  # set_fourier_fit: dict(n_modes, f, idx, freqf, common)
         self._os = None  # set_optimal_statistic: dict(G, nab, n_orf, centres, counts, target, template)
+        self._lnl = None  # set_likelihood_grid: dict(phi, axes, ld, target)
         self.segments = []  # (name, kind, f, amp, idx, L, mask) — host copy for checking/reporting
         names = signals
         if names is None:
@@ -347,6 +349,52 @@ class BatchSimulator:
         o = self._os
         Q, Qm, _ = self.ctx.batch_os(per_mode=per_mode)
         return _os.derive(Q, o["G"], o["nab"], o["n_orf"], o["centres"], o["counts"], Qm)
+
+    # ------------------------------------------------------------------ likelihood grid
+    def set_likelihood_grid(self, target=None, phi=None, log10_A=None, gamma=None, noise="layout", Mmats="tm",
+                            weights="white", rcond=None):
+        """Set the spectrum grid that likelihood_grid() applies to a block: per realization and grid point the Gaussian
+        log-likelihood ratio ln p(r | phi_g) - ln p(r | phi = 0) of the target process with the timing model
+        marginalised (the definition of include/fakepta_amd.h). Returns the kept design columns [P].
+
+        target:   a signal name of the noise model or its index; None picks the layout's only common signal
+                  (ValueError with none or several). Its own spectrum is not part of the base model: the grid replaces
+                  it. A common target is taken as uncorrelated between pulsars; a per-pulsar target gets the same
+                  spectrum for every pulsar.
+        phi:      the grid [G, N], the target's prior variance per grid point and mode (>= 0), or
+        log10_A, gamma: the axes of a power-law grid, phi = spectrum.powerlaw(f, A, gamma) * delta f, amplitude slowest.
+        noise:    "layout": every signal of this layout (f, amp^2, idx, mask); or a list of such segments. The other
+                  components stay at these values.
+        Mmats, weights, rcond: as set_fourier_fit; project() before likelihood_grid() changes nothing but rounding.
+
+        The weights are diagonal: ECORR is not part of them."""
+        segs = self.segments if isinstance(noise, str) and noise == "layout" else noise
+        if isinstance(segs, str):
+            raise ValueError(f"set_likelihood_grid: noise must be 'layout' or a list of segments, got {noise!r}")
+        t = _os.pick_target(segs, target)
+        model = _os.noise_model(segs, len(self.psrs))
+        grid, axes = _lnl.make_grid(_lnl.target_frequencies(model, t), phi, log10_A, gamma)
+        M, ncol = _os.design_of(self.psrs, Mmats, "set_likelihood_grid")
+        w = _tm.weights_of(self.psrs, weights, self.n_toa)
+        self._lnl = None
+        rank, ld = self.ctx.batch_set_lnl(model["n_modes"], model["f"], model["idx"], model["freqf"], model["phi"], t,
+                                          grid, masks=model["masks"], M=M, ncol_psr=ncol, weights=w, rcond=rcond)
+        self._lnl = dict(phi=grid, axes=axes, ld=ld, target=t)
+        return rank
+
+    def likelihood_grid(self, per_pulsar=False, posterior=False):
+        """The likelihood grid of every realization of the last block, computed on the device; the block is untouched.
+        A dict: dlnL [G, R] (or [nA, ngamma, R] for a grid built from axes), argmax (the maximum-likelihood grid point
+        per realization; with axes a tuple of index arrays, and log10_A_ml, gamma_ml [R]), lnB [R] = logsumexp_g(dlnL)
+        - ln G (the evidence ratio against "no process" under a uniform prior over the grid points), the axes log10_A
+        and gamma (None for an explicit grid), the normalised posterior with posterior=True, and q_psr, dlnL_psr
+        [P, G, R] with per_pulsar=True. Per batch of a sharded job: simulate_sharded(..., on_batch=lambda sim, first, n:
+        ...sim.likelihood_grid()...)."""
+        if getattr(self, "_lnl", None) is None:
+            raise ValueError("likelihood_grid: no likelihood grid is set; call set_likelihood_grid() first")
+        o = self._lnl
+        d, q, _ = self.ctx.batch_lnl(per_pulsar=per_pulsar)
+        return _lnl.derive(d, o["axes"], o["ld"], q, posterior)
 
     def synth_from_z(self, z):
         """Validation mode: z [n_real, n_seg, P, N_max, 2] standard normals (cos, sin)."""

@@ -1368,6 +1368,8 @@ int fpta_batch_set_toas(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const d
   c->fit_R = 0;
   c->has_os = false;  // the optimal statistic's operators too
   c->os_R = 0;
+  c->has_lnl = false;  // and the likelihood grid's
+  c->lnl_R = 0;
   c->out_R = 0;
   return layout_set_toas(c, c->batch, n_psr, offs, toas, nu);
 }

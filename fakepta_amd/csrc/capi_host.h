@@ -220,6 +220,14 @@ struct fpta_ctx {
   DevBuf os1_a, os1_offs, os1_rows, os1_res, os1_coef, os1_phi, os1_g, os1_qm, os1_q;
   bool has_os = false;
   int32_t os_K = 0, os_N = 0, os_J = 0, os_R = 0, os_rpad = 0;
+  // Likelihood grid (lnl.hip): k_fit_apply's third operator slot (B_p with the target left out of the model, CSR
+  // offsets, the rows to make per pulsar) and coefficient buffer X [P][K][lnl_rpad], the factors U [P][G][u_stride]
+  // (lnl_host.h's layout), the log-determinants [P][G] and the results q [P][G][lnl_rpad], dlnL [G][lnl_rpad] of the
+  // last fpta_batch_lnl (lnl_R realizations; 0: none); the same tables plus the residuals of one fpta_lnl_grid call
+  DevBuf lnl_a, lnl_offs, lnl_rows, lnl_coef, lnl_u, lnl_ld, lnl_q, lnl_d;
+  DevBuf lnl1_a, lnl1_offs, lnl1_rows, lnl1_res, lnl1_coef, lnl1_u, lnl1_ld, lnl1_q, lnl1_d;
+  bool has_lnl = false;
+  int32_t lnl_K = 0, lnl_N = 0, lnl_G = 0, lnl_R = 0, lnl_rpad = 0;
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
   int32_t out_R = 0;

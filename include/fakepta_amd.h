@@ -403,6 +403,62 @@ int fpta_os_statistic(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const d
                       const double* res /* [n_vec][n_toa_total] */, double* Q, double* Q_mode, double* X,
                       int32_t* rank_out, double* nab_out);
 
+/* Likelihood ratio of a common process on a spectrum grid: per realization of a block the Gaussian log-likelihood as a
+ * function of the target's spectrum, against "no such process", on G grid points (added without a change of
+ * FPTA_VERSION: no existing call changes). This text is the specification.
+ * The inputs are the optimal statistic's (above) without a template and pair weights: weights, a nuisance design M_p
+ * marginalised with infinite variance, C <= 8 components with prior variances phi [n_psr][sum_c N_c], one of them the
+ * target with N modes and K = 2 N <= 256 columns F_p. The target's own prior is not part of the base model (its phi
+ * entries are validated and otherwise ignored):
+ *   P0_p = W^-1 + sum_{c != target} F_c Phi_c F_c^T + M_p inf M_p^T.
+ * phi_grid [G][N] >= 0, 1 <= G <= 4096: row g is the target's prior variance per mode, the same for the cosine and the
+ * sine and for every pulsar (an uncorrelated common process when the target is a common signal; each pulsar's own noise
+ * surface when it is a per-pulsar signal). With X_p = F_p^T P0_p^-1 r_p and Z_p = F_p^T P0_p^-1 F_p:
+ *   C_pg = I + phi_g^(1/2) Z_p phi_g^(1/2)   (symmetric, eigenvalues >= 1),   C_pg = L L^T,
+ *   U_pg = L^-1 phi_g^(1/2)   (lower triangular; row and column of a mode with phi = 0 are zero),
+ *   ld_pg = 2 sum_i ln L_ii,   q[p][g][r] = |U_pg X_p,r|^2,
+ *   dlnL[g][r] = sum_p (q[p][g][r] - ld_pg) / 2, summed in pulsar order
+ *              = ln p(r | phi_g) - ln p(r | phi = 0) with the timing model marginalised.
+ * A pulsar without TOAs contributes exactly 0 and a grid row of zeros gives exactly 0. ECORR is not part of the
+ * weights; the other components stay at the values given.
+ * On the host, in long double with sums in index order: B_p = F_p^T P0_p^-1 by the optimal statistic's orthogonalisation
+ * with the target's phi = 0 (every target row takes the projection form), rounded once to fp64; Z_p = B_p F_p from the
+ * unrounded B_p; per grid point the Cholesky factor of C_pg, U_pg by forward substitution, rounded once to fp64, and
+ * ld_pg. The device holds B (8 K n_toa_total bytes) and U in 16-row groups with only the columns up to each group's
+ * diagonal block (8 * 128 * g (g + 1) bytes per pulsar and grid point, g = ceil(K / 16)); a failed allocation is
+ * FPTA_ENOMEM with the size in the message. X = B_p r comes from the Fourier fit's kernel (k_fit_apply) on a third
+ * operator slot with its own coefficient buffer, q from fp64 MFMA (k_lnl_quad: per row group only the k-steps up to
+ * its diagonal block, the squares summed in a fixed order, no atomics), dlnL from k_lnl_reduce; the per-pulsar terms
+ * (q - ld) / 2 added on the host in pulsar order equal dlnL bit for bit. A realization's results are bit-identical
+ * whatever the number of realizations, its position among them and its neighbours, and a grid point's whatever G. The
+ * block is read only. Validated on the host before anything is uploaded or launched (FPTA_EINVAL): everything the
+ * optimal statistic refuses of these inputs, K > 256, G outside [1, 4096], a grid entry that is negative or not finite
+ * (the message names the grid row and mode). Kernel time is booked under FPTA_K_DENSE, one entry per call.
+ *
+ * fpta_batch_set_lnl: the grid of the batch layout (after fpta_batch_set_toas, else FPTA_ESTATE). rank_out (NULL or
+ *   [n_psr]) gets the kept columns of M_p, ld_out (NULL or [n_psr][n_grid]) ld_pg. n_comp == 0 clears it, and so does
+ *   fpta_batch_set_toas. Independent of the timing model, the Fourier fit and the optimal statistic.
+ * fpta_batch_lnl_info: info[0] = K of the grid that is set (0: none), info[1] = N, info[2] = G, info[3] = the
+ *   realizations of the last fpta_batch_lnl result (0: none).
+ * fpta_batch_lnl: the grid of the context's last block on the context's stream (FPTA_ESTATE without a block or a
+ *   grid). dlnl NULL or [G][n_real], q_psr NULL or [n_psr][G][n_real], X NULL or [n_psr][K][n_real].
+ * fpta_lnl_grid: one call for any array and n_vec residual vectors res [n_vec][offs[n_psr]], independent of the batch
+ *   layout. U_out NULL or [n_psr][G][K][K]: the plan's fp64 U, dense, row-major, zeros above the diagonal. */
+int fpta_batch_set_lnl(fpta_ctx* ctx, int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                       const double* idx, const double* freqf, const double* phi /* [n_psr][sum_c N_c] */,
+                       const uint8_t* mask /* NULL or [n_comp][n_toa_total] */, int32_t target, int32_t n_col,
+                       const double* M /* [n_toa_total][n_col] */, const int32_t* ncol_psr, const double* weights,
+                       double rcond, int32_t n_grid, const double* phi_grid /* [n_grid][N_target] */,
+                       int32_t* rank_out, double* ld_out);
+int fpta_batch_lnl_info(fpta_ctx* ctx, int64_t* info /* [4] */);
+int fpta_batch_lnl(fpta_ctx* ctx, double* dlnl, double* q_psr, double* X);
+int fpta_lnl_grid(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const double* toas, const double* nu,
+                  int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common, const double* idx,
+                  const double* freqf, const double* phi, const uint8_t* mask, int32_t target, int32_t n_col,
+                  const double* M, const int32_t* ncol_psr, const double* weights, double rcond, int32_t n_grid,
+                  const double* phi_grid, int32_t n_vec, const double* res /* [n_vec][n_toa_total] */, double* dlnl,
+                  double* q_psr, double* X, int32_t* rank_out, double* ld_out, double* U_out);
+
 /* Replaces fakepta/fake_pta.py:201-230 (add_white_noise), with ECORR fixed (defects D1/D2):
  *   residuals[t] += sigma[t] * z[t]  +  sum over blocks b containing t: ecorr_sigma[b] * zb[b]
  * Blocks are CSR: block_offs[n_blocks+1] into block_idx (TOA indices, any order).
@@ -730,7 +786,8 @@ int fpta_build_flags(void);
                         * (fpta_batch_project, fpta_tm_project); k_fit_apply and k_fit_cross: one entry per call
                         * (fpta_batch_fit, fpta_fit_coefficients, fpta_batch_fit_cross); fpta_orf_anisotropic: one entry per
                           launch batch (k_orf_aniso + k_orf_reduce); fpta_batch_os, fpta_os_statistic: one entry per
-                          call (k_fit_apply + k_os_pairs + k_os_reduce) */
+                          call (k_fit_apply + k_os_pairs + k_os_reduce); fpta_batch_lnl, fpta_lnl_grid: one entry per
+                          call (k_fit_apply + k_lnl_quad + k_lnl_reduce) */
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
 #define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]);
                         * fpta_batch_cw_accumulate: one entry per call (k_cw_block, or those kernels + k_cw_bcast) */
