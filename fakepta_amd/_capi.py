@@ -43,6 +43,7 @@ _SIGS = [
     ("fpta_ephem_kepler", _c_int, [_ctx_p, _i64, _vp, _vp, _vp]),
     ("fpta_ephem_orbits", _c_int, [_ctx_p, _i64, _vp, _i32, _vp, _vp, _vp]),
     ("fpta_roemer_accumulate", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _dbl, _i32, _vp]),
+    ("fpta_batch_roemer_accumulate", _c_int, [_ctx_p, _vp, _i32, _vp, _vp, _dbl]),
     ("fpta_healpix_pix2ang_ring", _c_int, [_i32, _i64, _vp, _vp, _vp]),
     ("fpta_orf_anisotropic", _c_int, [_ctx_p, _i32, _vp, _i32, _i32, _vp, _vp]),
     ("fpta_orf_plan", _c_int, [_i32, _i32, _i64, _i32, _i64, _vp]),
@@ -138,11 +139,12 @@ OPT_GRID_WIDTH, OPT_GRID_SIGMA, OPT_GRID_MFMA, OPT_FUSE_CHECKSUMS = 7, 8, 9, 10
 OPT_MIX_MFMA, OPT_OVERLAP, OPT_INTERP_LDS, OPT_GRID_COALESCE, OPT_INTERP_WS, OPT_SIDE_SPLIT = 11, 12, 13, 14, 15, 16
 OPT_DFT_GEN, OPT_GEN_MIX, OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR = 17, 18, 19, 20, 21, 22
 OPT_INTERP_FUSED, OPT_FUSED_NEXT_MIX, OPT_CW_SPLIT, OPT_ORF_SPLIT = 23, 25, 26, 27  # key 24 is retired
+OPT_ROEMER_CHUNK = 28
 OPTIONS = (OPT_SYNTH_PATH, OPT_MFMA_MIN_REAL, OPT_PROFILE, OPT_ANCHOR, OPT_VALU_VARIANT, OPT_FUSE_WHITE,
            OPT_GRID_WIDTH, OPT_GRID_SIGMA, OPT_GRID_MFMA, OPT_FUSE_CHECKSUMS, OPT_MIX_MFMA, OPT_OVERLAP,
            OPT_INTERP_LDS, OPT_GRID_COALESCE, OPT_INTERP_WS, OPT_SIDE_SPLIT, OPT_DFT_GEN, OPT_GEN_MIX,
            OPT_ASYNC_SUMS, OPT_PART_GROUP, OPT_INTERP_PSR, OPT_INTERP_WR, OPT_INTERP_FUSED, OPT_FUSED_NEXT_MIX,
-           OPT_CW_SPLIT, OPT_ORF_SPLIT)
+           OPT_CW_SPLIT, OPT_ORF_SPLIT, OPT_ROEMER_CHUNK)
 K_GEN, K_MIX, K_SYNTH, K_WHITE, K_DENSE, K_GRID, K_CW, K_EPHEM = 0, 1, 2, 3, 4, 5, 6, 7
 CW_NPAR = 9  # FPTA_CW_NPAR: cos_gwtheta, gwphi, cos_inc, log10_mc, log10_fgw, log10_h, phase0, psi, psrterm
 EPHEM_NBODY = 14  # FPTA_EPHEM_NBODY: mass, T, then (value, rate per century) of inc, Om, omega, a, e, l0
@@ -460,6 +462,26 @@ class Context:
         self._check(_lib.fpta_roemer_accumulate(self._h, P, _ptr(offs), _ptr(toas), _ptr(pos), len(rows), _ptr(rows),
                                                 float(sign), int(bool(separate)), _ptr(out)),
                     "fpta_roemer_accumulate")
+
+    def batch_roemer_accumulate(self, pos, n_tab, row_offs, rows, sign=1.0):
+        """Roemer delays of ephemeris errors added to every realization of the last batch block, in place on the
+        device (fpta_batch_roemer_accumulate). pos [P, 3] for the batch layout's pulsars; n_tab 1 (one table for all)
+        or R tables in CSR form: table r is rows[row_offs[r]:row_offs[r + 1]], rows of ROEMER_NPAR values
+        (fakepta_amd.ephem.perturbation_tables makes the three)."""
+        P = self.batch_info()["n_psr"]
+        if P == 0:  # no layout to check the shapes against: the library's own state error
+            raise FptaError("fpta_batch_roemer_accumulate failed (-77): batch_roemer_accumulate: set_toas first")
+        pos = _f64(pos)
+        row_offs = np.ascontiguousarray(row_offs, dtype=np.int64)
+        rows = _f64(rows).reshape(-1, ROEMER_NPAR)
+        n_tab = int(n_tab)
+        if pos.shape != (P, 3):
+            raise ValueError(f"batch_roemer_accumulate: expected pos [{P}, 3], got {pos.shape}")
+        if n_tab < 0 or row_offs.shape != (n_tab + 1,) or (len(row_offs) and row_offs[-1] != len(rows)):
+            raise ValueError(f"batch_roemer_accumulate: row_offs must hold {n_tab + 1} offsets ending at the "
+                             f"{len(rows)} rows")
+        self._check(_lib.fpta_batch_roemer_accumulate(self._h, _ptr(pos), n_tab, _ptr(row_offs), _ptr(rows),
+                                                      float(sign)), "fpta_batch_roemer_accumulate")
 
     def orf_anisotropic(self, pos, nside, h_maps, out=None):
         """ORFs [M, P, P] of the maps h_maps [M, 12 nside^2] (HEALPix RING) for pulsars at the unit vectors pos [P, 3]

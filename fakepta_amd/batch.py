@@ -237,6 +237,38 @@ class BatchSimulator:
                           for i, d in enumerate(pdist)], axis=-1)
         self.ctx.batch_cw_accumulate(pos, L, n_tab, src_offs, src, sign=sign)
 
+    # ------------------------------------------------------------------ ephemeris errors
+    def add_roemer_delay(self, perturbations, sign=1.0, ephem=None):
+        """Add the Roemer delays of solar-system-ephemeris errors (fakepta_amd.ephem, the signal of
+        correlated_noises.add_roemer_delay) to every realization of the last block, in place on the device: downloads,
+        checksums(), correlations(), hd_curve(), project(), fourier_fit(), optimal_statistic() and likelihood_grid()
+        afterwards see the block with the delays. The next synth() is not affected.
+
+        perturbations: one table for every realization (an [n, 22] array of ephem.ROW_COLUMNS rows, or a list of
+                 (planet, deviations) as add_roemer_delay_array takes), or one table per realization: an [R, n, 22]
+                 array or a list of R tables of either form (ephem.perturbation_tables); a table may be empty.
+        sign:    -1.0 takes the same delays out again (to rounding).
+        ephem:   the Ephemeris that resolves planets given by name; default the native one every pulsar shares.
+                 Tables of rows need none.
+
+        Every pulsar needs pos. A bad row (named by realization and index) or a missing block raises the library's
+        error and leaves the block as it was. Realization r gets what add_roemer_delay_array adds for its table. In a
+        sharded run the injection goes into the consumer:
+            simulate_sharded(sim, n_real, on_batch=lambda sim, first, n: (sim.add_roemer_delay(pert[first:first + n]),
+                                                                           sim.project()))"""
+        from . import ephem as _ephem
+        from fakepta.correlated_noises import _native_ephem
+        P = len(self.psrs)
+        try:
+            pos = np.array([np.asarray(p.pos, dtype=np.float64) for p in self.psrs]).reshape(P, 3)
+        except AttributeError as e:
+            raise ValueError(f"add_roemer_delay: every pulsar needs pos ({e})") from None
+        _, _, R = self.ctx.batch_device_out()  # the library's state error without a block
+        if ephem is None and all(hasattr(p, "ephem") for p in self.psrs):
+            ephem = _native_ephem(self.psrs)
+        n_tab, row_offs, rows = _ephem.perturbation_tables(perturbations, R, ephem=ephem)
+        self.ctx.batch_roemer_accumulate(pos, n_tab, row_offs, rows, sign=sign)
+
     # ------------------------------------------------------------------ Fourier fit
     def set_fourier_fit(self, components=None, Mmats="tm", weights="white", rcond=None, common=None):
         """Set the Fourier fit that fourier_fit(), power_spectrum(), cross_spectrum() and hd_curve(domain="fourier")

@@ -1012,6 +1012,10 @@ int fpta_set_option(fpta_ctx* c, int32_t key, int64_t value) {
       if (value < 0) return fail(c, FPTA_EINVAL, "orf_split must be >= 0");
       c->orf_split = value;
       return FPTA_OK;
+    case FPTA_OPT_ROEMER_CHUNK:
+      if (value < 0) return fail(c, FPTA_EINVAL, "roemer_chunk must be >= 0");
+      c->roemer_chunk = value;
+      return FPTA_OK;
     case FPTA_OPT_INTERP_WR:
 #ifndef FPTA_DIAG_KERNELS
       if (value) return fail(c, FPTA_EINVAL, "interp_wr: k_grid_interp_wr is a diagnostic kernel, not in this build");
@@ -1083,6 +1087,7 @@ int fpta_get_option(fpta_ctx* c, int32_t key, int64_t* value) {
     case FPTA_OPT_FUSED_NEXT_MIX: *value = c->fused_next_mix; return FPTA_OK;
     case FPTA_OPT_CW_SPLIT: *value = c->cw_split; return FPTA_OK;
     case FPTA_OPT_ORF_SPLIT: *value = c->orf_split; return FPTA_OK;
+    case FPTA_OPT_ROEMER_CHUNK: *value = c->roemer_chunk; return FPTA_OK;
   }
   return fail(c, FPTA_EINVAL, "get_option: unknown key");
 }

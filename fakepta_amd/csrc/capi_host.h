@@ -196,6 +196,11 @@ struct fpta_ctx {
   // fpta_ephem_* / fpta_roemer_accumulate (ephem.hip): TOAs (or M), the body / row table (or e), pulsar positions,
   // the 64-TOA wave table, the output (planetssb, delays, residuals or E) and sunssb
   DevBuf eph_toas, eph_tab, eph_pos, eph_waves, eph_out, eph_sun;
+  // fpta_batch_roemer_accumulate (roemer_batch.hip): pulsar positions, the CSR offsets of the row tables, the row
+  // records of all realizations and their base slots, the slots' bodies, the 256-TOA slab table, and the delay vector
+  // [n_toa] of the one-table mode
+  DevBuf rmb_pos, rmb_offs, rmb_rows, rmb_slots, rmb_bases, rmb_slabs, rmb_v;
+  int64_t roemer_chunk = 0;  // FPTA_OPT_ROEMER_CHUNK: 0 auto (fpta_roemerb::chunk_size), n >= 1 forces n (clamped to 32)
   // fpta_orf_anisotropic (orf.hip): pulsar positions, the HEALPix ring table, the maps, the K-split partial tiles of
   // one launch, the ORFs of one launch
   DevBuf orf_pos, orf_rings, orf_h, orf_part, orf_out;

@@ -28,7 +28,6 @@ using fpta_cwb::Slab;
 
 constexpr int kCwbThreads = fpta_cwb::kSlabToas;  // one TOA per thread
 constexpr int kCwbTile = 128;                     // sources of one LDS tile (4 KB of pairs)
-constexpr int kCwbRows = 8;                       // realizations per thread of k_cw_bcast
 static_assert(kCwbTile <= kCwbThreads, "one thread per source of a tile");
 
 // a wave-uniform double held in vector registers, as a scalar value

@@ -9,83 +9,13 @@
 //   k_roemer_main   one wave per 64 TOAs of one pulsar, looping over the rows in ascending order: the sum of the
 //                   delays into the residuals, or every row's delay into its own output row
 // The body and row tables are indexed by wave-uniform values only, so they come through the scalar cache. No LDS, no
-// atomics.
+// atomics. The orbit arithmetic is ephem_device.h, shared with roemer_batch.hip.
 #include "capi_host.h"
+#include "ephem_device.h"
 #include "ephem_host.h"
 #include "device_common.h"
 
 namespace __attribute__((visibility("hidden"))) capi {
-
-using fpta_ephem::Body;
-using fpta_ephem::RoemerRow;
-
-struct EphWave {
-  int64_t first;  // first TOA (index into the concatenated arrays)
-  int32_t psr;
-  int32_t count;  // 1 .. 64
-};
-
-constexpr int kEphWave = 64;
-constexpr double kDegToRad = fpta_ephem::kPi / 180.0;
-constexpr double kAuOverC = fpta_ephem::kAU / fpta_ephem::kC;  // light-seconds per AU
-
-struct Vec3 {
-  double x, y, z;
-};
-
-// E - e sin E = M for M in [0, 2 pi) and 0 <= e <= kEMax: Newton with the analytic derivative. From pi the iterates
-// are monotone for every e < 1 (the function is convex below pi and concave above); M + e sin M is closer at low e.
-// The cap is never reached: tests/ephem_reference.py kepler_newton is this loop in numpy.
-__device__ __forceinline__ double kepler_solve(double M, double e) {
-  double E = e < fpta_ephem::kLowE ? M + e * sin(M) : fpta_ephem::kPi;
-  for (int it = 0; it < fpta_ephem::kKeplerMaxIter; ++it) {
-    double sn, cs;
-    sincos(E, &sn, &cs);
-    const double dE = ((E - e * sn) - M) / (1.0 - e * cs);
-    E -= dE;
-    if (fabs(dE) <= fpta_ephem::kKeplerTol) break;
-  }
-  return E;
-}
-
-// Position in the orbital plane. x is the reference's a cos(E - e), not the textbook a (cos E - e): kept so that
-// seeded scripts reproduce. This is the one place to change it.
-__device__ __forceinline__ void orbit_in_plane(double a_s, double e, double E, double& x, double& y) {
-  x = a_s * cos(E - e);
-  y = a_s * sqrt((1.0 - e) * (1.0 + e)) * sin(E);
-}
-
-// Julian centuries from J2000: (toa / 86400 - 51544.5) / 36525 with the rounding of the first quotient carried along
-// (the subtraction of 51544.5 is exact for any MJD of this or the last century)
-__device__ __forceinline__ double centuries(double toa) {
-  const double d = toa / 86400.0;
-  const double r = fma(-d, 86400.0, toa);
-  return ((d - fpta_ephem::kMjdJ2000) + r * (1.0 / 86400.0)) / 36525.0;
-}
-
-// Equatorial position [light-seconds] of body b at t centuries; (se, ce) the obliquity's sine and cosine.
-__device__ __forceinline__ Vec3 orbit_eq(const Body& b, double t, double se, double ce) {
-  const double inc = fma(b.inc_rate, t, b.inc), Om = fma(b.Om_rate, t, b.Om), omega = fma(b.omega_rate, t, b.omega);
-  const double a_s = fma(b.a_rate, t, b.a) * kAuOverC;
-  const double e = fma(b.e_rate, t, b.e), l0 = fma(b.l0_rate, t, b.l0);
-  // mean anomaly: reduced in degrees, where the reduction is exact
-  double md = l0 - omega;
-  md = fma(-floor(md / 360.0), 360.0, md);
-  if (md < 0.0) md += 360.0;
-  if (md >= 360.0) md -= 360.0;
-  const double E = kepler_solve(md * kDegToRad, e);
-  double x, y;
-  orbit_in_plane(a_s, e, E, x, y);
-  // the first two columns of the (Om, omega - Om, inc) rotation: z is 0 in the plane
-  double sO, cO, sw, cw, si, ci;
-  sincos(Om * kDegToRad, &sO, &cO);
-  sincos((omega - Om) * kDegToRad, &sw, &cw);
-  sincos(inc * kDegToRad, &si, &ci);
-  const double X = (cO * cw - sO * ci * sw) * x + (-cO * sw - sO * ci * cw) * y;
-  const double Y = (sO * cw + cO * ci * sw) * x + (-sO * sw + cO * ci * cw) * y;
-  const double Z = si * sw * x + si * cw * y;
-  return {X, ce * Y - se * Z, se * Y + ce * Z};  // ecliptic -> equatorial
-}
 
 __global__ __launch_bounds__(256) void k_ephem_kepler(int64_t n, const double* __restrict__ M,
                                                        const double* __restrict__ e, double* __restrict__ E) {
@@ -166,6 +96,33 @@ __global__ __launch_bounds__(kEphWave) void k_roemer_main(const EphWave* __restr
     }
   }
   if (!SEPARATE && live) dst[i] += sign * acc;
+}
+
+// 64-TOA waves of every pulsar, in TOA order; a pulsar without TOAs gets none
+static void make_waves(int32_t n_psr, const int64_t* offs, std::vector<EphWave>& waves) {
+  waves.clear();
+  for (int32_t p = 0; p < n_psr; ++p)
+    for (int64_t i = offs[p]; i < offs[p + 1]; i += kEphWave)
+      waves.push_back({i, p, (int32_t)std::min<int64_t>(kEphWave, offs[p + 1] - i)});
+}
+
+int roemer_sum_launch(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const double* toas, const double* pos,
+                      const std::vector<RoemerRow>& rows, double sign, int64_t n_toa, std::vector<EphWave>& waves,
+                      double* dst) {
+  make_waves(n_psr, offs, waves);
+  if (waves.empty() || rows.empty()) return FPTA_OK;
+  if (waves.size() > (size_t)0x7FFFFFFF || rows.size() > (size_t)0x7FFFFFFF)
+    return fail(c, FPTA_EINVAL, "roemer: too many TOAs or rows");
+  const fpta_ephem::Obliquity ob = fpta_ephem::obliquity();
+  int rc;
+  if ((rc = upload(c, c->eph_pos, pos, sizeof(double) * 3 * (size_t)n_psr, "roemer pos"))) return rc;
+  if ((rc = upload(c, c->eph_tab, rows.data(), sizeof(RoemerRow) * rows.size(), "roemer rows"))) return rc;
+  if ((rc = upload(c, c->eph_waves, waves.data(), sizeof(EphWave) * waves.size(), "roemer waves"))) return rc;
+  k_roemer_main<false><<<dim3((unsigned)waves.size()), dim3(kEphWave), 0, c->stream>>>(
+      c->eph_waves.as<EphWave>(), toas, c->eph_pos.as<double>(), c->eph_tab.as<RoemerRow>(), (int32_t)rows.size(),
+      ob.sn, ob.cs, sign, n_toa, dst);
+  HIPCHK(c, hipGetLastError(), "k_roemer_main launch");
+  return FPTA_OK;
 }
 
 }  // namespace capi
@@ -275,9 +232,7 @@ extern "C" int fpta_roemer_accumulate(fpta_ctx* c, int32_t n_psr, const int64_t*
   if (bad >= 0) return fail(c, FPTA_EINVAL, "roemer_accumulate: row " + std::to_string(bad) + ": " + why);
   if (n_row == 0 || n_toa == 0) return FPTA_OK;
   std::vector<EphWave> waves;
-  for (int32_t p = 0; p < n_psr; ++p)
-    for (int64_t i = offs[p]; i < offs[p + 1]; i += kEphWave)
-      waves.push_back({i, p, (int32_t)std::min<int64_t>(kEphWave, offs[p + 1] - i)});
+  make_waves(n_psr, offs, waves);
   if (waves.size() > (size_t)0x7FFFFFFF) return fail(c, FPTA_EINVAL, "roemer_accumulate: too many TOAs");
   const fpta_ephem::Obliquity ob = fpta_ephem::obliquity();
   const size_t n_out = (size_t)n_toa * (separate ? (size_t)n_row : 1);

@@ -1,7 +1,9 @@
 """Solar-system ephemeris and Roemer delay on the GPU (fpta_ephem_kepler, fpta_ephem_orbits,
 fpta_roemer_accumulate, csrc/ephem.hip): Keplerian orbits with linearly drifting elements for any number of bodies,
 and the Roemer delay of ephemeris errors for a whole array in one call. fakepta.ephemeris.Ephemeris is the
-reference's class on top of this module. The definition is restated in include/fakepta_amd.h."""
+reference's class on top of this module. perturbation_tables makes the per-realization row tables that
+BatchSimulator.add_roemer_delay (fpta_batch_roemer_accumulate, csrc/roemer_batch.hip) injects into a resident block.
+The definition is restated in include/fakepta_amd.h."""
 import numpy as np
 
 from . import _capi
@@ -62,6 +64,61 @@ def row_table(rows):
     if tab.ndim != 2 or tab.shape[1] != len(ROW_COLUMNS):
         raise ValueError(f"rows must be [R, {len(ROW_COLUMNS)}] ({', '.join(ROW_COLUMNS)})")
     return np.ascontiguousarray(tab)
+
+
+def _is_perturbation(x):
+    return isinstance(x, (tuple, list)) and len(x) == 2 and isinstance(x[1], dict)
+
+
+def _one_table(tab, ephem):
+    """[n, 22] from rows or from a list of (planet, deviations); anything empty is the empty table."""
+    if isinstance(tab, (list, tuple)) and len(tab) and all(_is_perturbation(x) for x in tab):
+        if ephem is None:
+            raise ValueError("perturbation_tables: planets given by name need an Ephemeris (ephem=)")
+        return row_table([ephem.roemer_row(planet, **dev) for planet, dev in tab])
+    if np.size(tab) == 0:
+        return np.zeros((0, len(ROW_COLUMNS)))
+    return row_table(tab)
+
+
+def _is_table(x):
+    if isinstance(x, (list, tuple)) and len(x) and all(_is_perturbation(p) for p in x):
+        return True
+    return np.size(x) == 0 or np.ndim(x) == 2
+
+
+def perturbation_tables(perts, R, ephem=None):
+    """(n_tab, row_offs [n_tab + 1] int64, rows [total, 22] float64): the row tables of a block of R realizations in the
+    CSR form fpta_batch_roemer_accumulate takes. perts is one table for every realization (an [n, 22] array of
+    ROW_COLUMNS rows, one row, or a list of (planet, deviations) as add_roemer_delay_array takes, resolved through
+    ephem.roemer_row: n_tab 1), an [R, n, 22] array, or a list of R tables of either form and any lengths (an empty
+    one included). Needs no device."""
+    R = int(R)
+    if R < 1:
+        raise ValueError(f"perturbation_tables: R must be >= 1, got {R}")
+    ncol = len(ROW_COLUMNS)
+    per_real = None
+    if isinstance(perts, (list, tuple)) and len(perts) and all(_is_perturbation(x) for x in perts):
+        tab = _one_table(perts, ephem)
+    elif isinstance(perts, (list, tuple)) and len(perts) and all(_is_table(t) for t in perts):
+        per_real = [_one_table(t, ephem) for t in perts]
+    else:
+        arr = np.asarray(perts, dtype=np.float64)
+        if arr.ndim == 3:
+            if arr.shape[2] != ncol:
+                raise ValueError(f"perturbation_tables: rows [R, n, {ncol}] expected, got {arr.shape}")
+            per_real = list(arr)
+        elif arr.ndim > 3:
+            raise ValueError(f"perturbation_tables: rows [n, {ncol}] or [R, n, {ncol}] expected, got {arr.shape}")
+        else:
+            tab = _one_table(arr, ephem)
+    if per_real is None:
+        return 1, np.array([0, len(tab)], dtype=np.int64), tab
+    if len(per_real) != R:
+        raise ValueError(f"perturbation_tables: {len(per_real)} tables for {R} realizations")
+    offs = np.concatenate([[0], np.cumsum([len(t) for t in per_real])]).astype(np.int64)
+    rows = np.concatenate(per_real, axis=0) if offs[-1] else np.zeros((0, ncol))
+    return R, offs, np.ascontiguousarray(rows, dtype=np.float64)
 
 
 def kepler(M, e):

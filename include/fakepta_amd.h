@@ -189,6 +189,26 @@ int fpta_roemer_accumulate(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, co
                            const double* pos /* [n_psr][3] */, int32_t n_row,
                            const double* rows /* [n_row][FPTA_ROEMER_NPAR] */, double sign, int32_t separate,
                            double* out);
+/* The same delays injected into the context's last batch block, in place on the device (added without a change of
+ * FPTA_VERSION: no existing call changes): for every realization r of the block and every TOA t of the batch layout,
+ *   block[r][t in p] += sign * sum_k delay_k(t in p),   k over the rows of table r,
+ * delay_k as above, summed over k in ascending order in one register, and sign * sum rounded as a product before it is
+ * added. n_tab == the block's realization count: table r is the rows row_offs[r] .. row_offs[r + 1] - 1 of rows (CSR; a
+ * table may be empty, and its realization is not touched), and realization r equals, bit for bit, its samples plus what
+ * fpta_roemer_accumulate (separate == 0) adds to zeros for table r, whatever FPTA_OPT_ROEMER_CHUNK. n_tab == 1: one
+ * table for every realization; its delay vector is made once with fpta_roemer_accumulate's own kernel on zeros and
+ * added to every realization. pos [P][3]: the batch layout's pulsars. FPTA_ESTATE without a synthesized block.
+ * Validated on the host before anything is uploaded or launched (FPTA_EINVAL, the block untouched): n_tab not 1 or the
+ * block's realization count, row_offs not starting at 0 or not monotone, a non-finite sign or position, and every row
+ * as fpta_roemer_accumulate validates it over the layout's TOA span ("realization r, row k: reason"). No rows at all is
+ * a successful no-op. It runs on the context's stream and returns when the block is updated; fpta_batch_download,
+ * _checksums, _correlations, _project, _fit, _os and _lnl afterwards see the block with the delays; the next block is
+ * not affected. Blocks streamed by fpta_batch_synth_checksums / fpta_multi_synth get no delays. Kernel time is booked
+ * under FPTA_K_EPHEM, one entry per call. */
+int fpta_batch_roemer_accumulate(fpta_ctx* ctx, const double* pos /* [P][3] */,
+                                 int32_t n_tab /* 1: one table for every realization; else == the block's n_real */,
+                                 const int64_t* row_offs /* [n_tab + 1] */,
+                                 const double* rows /* [row_offs[n_tab]][FPTA_ROEMER_NPAR] */, double sign);
 
 /* Replaces fakepta/correlated_noises.py:73-89 (anisotropic: healpy's pix2ang and one antenna-pattern call per pulsar
  * pair) for any number of maps in one call (added without a change of FPTA_VERSION: no existing call changes). This
@@ -768,6 +788,11 @@ int fpta_comm_gather(fpta_comm* comm, const double* send, int64_t count, double*
 #define FPTA_OPT_ORF_SPLIT 27      /* fpta_orf_anisotropic: 0 (default) auto: the pixel range is cut into K-splits
                                      until the tiles fill the device (a pure function of n_psr and nside,
                                      fpta_orf_plan); n >= 1 forces n K-splits (clamped to the chunk count). */
+#define FPTA_OPT_ROEMER_CHUNK 28   /* fpta_batch_roemer_accumulate with one table per realization: consecutive
+                                     realizations that one k_roemer_block workgroup serves with one evaluation of the
+                                     base orbits. 0 (default) auto: n_slab n_real / 1024 (n_slab the 256-TOA slabs of
+                                     the layout), within 1 .. 32; n >= 1 forces n (clamped to 32). Results are
+                                     identical. */
 int fpta_set_option(fpta_ctx* ctx, int32_t key, int64_t value);
 /* Current value of option `key` (same keys as fpta_set_option). */
 int fpta_get_option(fpta_ctx* ctx, int32_t key, int64_t* value);
@@ -791,7 +816,9 @@ int fpta_build_flags(void);
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
 #define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]);
                         * fpta_batch_cw_accumulate: one entry per call (k_cw_block, or those kernels + k_cw_bcast) */
-#define FPTA_K_EPHEM 7 /* fpta_ephem_kepler / fpta_ephem_orbits / fpta_roemer_accumulate: one entry per call */
+#define FPTA_K_EPHEM 7 /* fpta_ephem_kepler / fpta_ephem_orbits / fpta_roemer_accumulate: one entry per call;
+                        * fpta_batch_roemer_accumulate: one entry per call (k_roemer_block, or k_roemer_main +
+                        * k_cw_bcast) */
 #define FPTA_K_N 8
 /* Accumulated launches and HIP-event milliseconds of kernel `which` since the last reset. */
 int fpta_kernel_stats(fpta_ctx* ctx, int32_t which, int64_t* count, double* total_ms);
