@@ -501,10 +501,11 @@ class Context:
         return out
 
     @staticmethod
-    def _tm_args(what, P, n, M, ncol_psr, weights):
-        """The design matrix [n, n_col], column counts [P] or None and weights [n] or None of a timing-model call, as
-        contiguous arrays of the C types."""
-        M = _f64(M)
+    def _tm_args(what, P, n, M, ncol_psr, weights, rcond=None):
+        """The design matrix [n, n_col] (None: no column), column counts [P] or None, weights [n] or None and rcond
+        (None: the library's default, 0) of a call that fits a design out, as contiguous arrays of the C types and a
+        float."""
+        M = np.zeros((n, 0)) if M is None else _f64(M)
         if M.ndim != 2 or M.shape[0] != n or M.shape[1] > TM_MAX_COL:
             raise ValueError(f"{what}: M must be [{n}, n_col <= {TM_MAX_COL}], got {M.shape}")
         if ncol_psr is not None:
@@ -515,25 +516,54 @@ class Context:
             weights = _f64(weights)
             if weights.shape != (n,):
                 raise ValueError(f"{what}: weights must hold {n} values")
-        return M, ncol_psr, weights
+        return M, ncol_psr, weights, 0.0 if rcond is None else float(rcond)
+
+    @staticmethod
+    def _offs_args(what, offs):
+        """The CSR offsets [P + 1] of a one-shot call as int64, with P and n_toa."""
+        offs = np.ascontiguousarray(offs, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1:
+            raise ValueError(f"{what}: offs must be [P + 1]")
+        return offs, len(offs) - 1, int(offs[-1])
+
+    @classmethod
+    def _oneshot_args(cls, what, offs, toas, nu, res):
+        """The array and the vectors of a one-shot call that reads res [n_vec, n_toa] or [n_toa]: offs, toas, nu and res
+        as contiguous arrays of the C types, with P, n_toa and n_vec."""
+        offs, P, n = cls._offs_args(what, offs)
+        toas, nu, res = _f64(toas), _f64(nu), _f64(res)
+        if toas.shape != (n,) or nu.shape != (n,):
+            raise ValueError(f"{what}: toas and nu must hold {n} values")
+        if res.ndim not in (1, 2) or res.shape[-1] != n:
+            raise ValueError(f"{what}: res must be [n_vec, {n}] or [{n}], got {res.shape}")
+        return offs, toas, nu, res, P, n, 1 if res.ndim == 1 else res.shape[0]
+
+    def _info4(self, fn, what):
+        """The four integers of a fpta_batch_*_info call."""
+        info = np.zeros(4, dtype=np.int64)
+        self._check(fn(self._h, _ptr(info)), what)
+        return [int(v) for v in info]
+
+    def _block_real(self):
+        """R of the resident block, or 0 without one (the library's state error follows from the call itself)."""
+        try:
+            return self.batch_device_out()[2]
+        except FptaError:
+            return 0
 
     def tm_project(self, offs, M, res, ncol_psr=None, weights=None, rcond=None):
         """The weighted least-squares fit of the design matrices M [n_toa, n_col] (pulsar p: rows offs[p] ..
         offs[p + 1], its leading ncol_psr[p] columns) removed from every row of res [n_vec, n_toa] or [n_toa], in place
         (fpta_tm_project). Returns the ranks [P]."""
-        offs = np.ascontiguousarray(offs, dtype=np.int64)
-        if offs.ndim != 1 or len(offs) < 1:
-            raise ValueError("tm_project: offs must be [P + 1]")
-        P, n = len(offs) - 1, int(offs[-1])
-        M, ncol_psr, weights = self._tm_args("tm_project", P, n, M, ncol_psr, weights)
+        offs, P, n = self._offs_args("tm_project", offs)
+        M, ncol_psr, weights, rcond = self._tm_args("tm_project", P, n, _f64(M), ncol_psr, weights, rcond)
         if not (isinstance(res, np.ndarray) and res.dtype == np.float64 and res.flags.c_contiguous
                 and res.flags.writeable and res.ndim in (1, 2) and res.shape[-1] == n):
             raise ValueError(f"tm_project: res must be a writable contiguous float64 array [n_vec, {n}] or [{n}]")
         n_vec = 1 if res.ndim == 1 else res.shape[0]
         rank = np.zeros(P, dtype=np.int32)
         self._check(_lib.fpta_tm_project(self._h, P, _ptr(offs), _ptr(M), M.shape[1], _ptr(ncol_psr), _ptr(weights),
-                                         0.0 if rcond is None else float(rcond), n_vec, _ptr(res), _ptr(rank)),
-                    "fpta_tm_project")
+                                         rcond, n_vec, _ptr(res), _ptr(rank)), "fpta_tm_project")
         return rank
 
     def white_accumulate(self, sigma, z, residuals, blocks=None, ecorr_sigma=None, zb=None):
@@ -584,12 +614,9 @@ class Context:
         rank = np.zeros(P, dtype=np.int32)
         if P == 0:  # no layout to check M against: the library's own state error
             raise FptaError("fpta_batch_set_timing_model failed (-77): set_timing_model: set_toas first")
-        if M is None:
-            M = np.zeros((n, 0))
-        M, ncol_psr, weights = self._tm_args("batch_set_timing_model", P, n, M, ncol_psr, weights)
+        M, ncol_psr, weights, rcond = self._tm_args("batch_set_timing_model", P, n, M, ncol_psr, weights, rcond)
         self._check(_lib.fpta_batch_set_timing_model(self._h, M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
-                                                     0.0 if rcond is None else float(rcond), _ptr(rank)),
-                    "fpta_batch_set_timing_model")
+                                                     rcond, _ptr(rank)), "fpta_batch_set_timing_model")
         return rank
 
     def batch_project(self):
@@ -597,15 +624,16 @@ class Context:
         self._check(_lib.fpta_batch_project(self._h), "fpta_batch_project")
 
     @staticmethod
-    def _fit_args(what, P, n_modes, f, idx, freqf):
-        """The component tables of a Fourier-fit call as contiguous arrays of the C types: n_modes [n_comp] int32, f
-        [sum N_c] (common) or [P, sum N_c], idx and freqf [n_comp]. Returns them and whether f is common."""
+    def _fit_args(what, P, n_modes, f, idx, freqf, max_comp=FIT_MAX_COMP, max_col=FIT_MAX_COEF):
+        """The component tables of a Fourier-fit call as contiguous arrays of the C types: n_modes [n_comp] int32 (up
+        to max_comp components and max_col columns), f [sum N_c] (common) or [P, sum N_c], idx and freqf [n_comp].
+        Returns them and whether f is common."""
         n_modes = np.ascontiguousarray(n_modes, dtype=np.int32)
-        if n_modes.ndim != 1 or not 1 <= len(n_modes) <= FIT_MAX_COMP or np.any(n_modes < 1):
-            raise ValueError(f"{what}: n_modes must hold 1 .. {FIT_MAX_COMP} positive mode counts, got {n_modes}")
+        if n_modes.ndim != 1 or not 1 <= len(n_modes) <= max_comp or np.any(n_modes < 1):
+            raise ValueError(f"{what}: n_modes must hold 1 .. {max_comp} positive mode counts, got {n_modes}")
         n_f = int(n_modes.sum())
-        if 2 * n_f > FIT_MAX_COEF:
-            raise ValueError(f"{what}: {2 * n_f} Fourier columns, more than {FIT_MAX_COEF}")
+        if 2 * n_f > max_col:
+            raise ValueError(f"{what}: {2 * n_f} Fourier columns, more than {max_col}")
         f = _f64(f)
         if f.shape not in ((n_f,), (P, n_f)):
             raise ValueError(f"{what}: f must be [{n_f}] or [{P}, {n_f}], got {f.shape}")
@@ -627,22 +655,18 @@ class Context:
                                                 _ptr(rank), None), "fpta_batch_set_fit")
             return rank, np.zeros((P, 0), dtype=bool)
         n_modes, f, idx, freqf, common = self._fit_args("batch_set_fit", P, n_modes, f, idx, freqf)
-        if M is None:
-            M = np.zeros((n, 0))
-        M, ncol_psr, weights = self._tm_args("batch_set_fit", P, n, M, ncol_psr, weights)
+        M, ncol_psr, weights, rcond = self._tm_args("batch_set_fit", P, n, M, ncol_psr, weights, rcond)
         kept = np.zeros((P, 2 * int(n_modes.sum())), dtype=np.uint8)
         self._check(_lib.fpta_batch_set_fit(self._h, len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx),
-                                            _ptr(freqf), M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
-                                            0.0 if rcond is None else float(rcond), _ptr(rank), _ptr(kept)),
-                    "fpta_batch_set_fit")
+                                            _ptr(freqf), M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights), rcond,
+                                            _ptr(rank), _ptr(kept)), "fpta_batch_set_fit")
         return rank, kept.astype(bool)
 
     def batch_fit_info(self):
         """K and mode count of the fit that is set (0: none), whether its grid is common, and the realizations of the
         last fit result (fpta_batch_fit_info)."""
-        info = np.zeros(4, dtype=np.int64)
-        self._check(_lib.fpta_batch_fit_info(self._h, _ptr(info)), "fpta_batch_fit_info")
-        return dict(K=int(info[0]), n_mode=int(info[1]), common=bool(info[2]), n_real=int(info[3]))
+        K, n_mode, common, n_real = self._info4(_lib.fpta_batch_fit_info, "fpta_batch_fit_info")
+        return dict(K=K, n_mode=n_mode, common=bool(common), n_real=n_real)
 
     def batch_fit(self, K=None, to_host=True):
         """Fit the last block (fpta_batch_fit): [P, K, R] on the host, or None with the result left on the device.
@@ -653,11 +677,7 @@ class Context:
         if not to_host:
             self._check(_lib.fpta_batch_fit(self._h, None), "fpta_batch_fit")
             return None
-        try:
-            _, _, R = self.batch_device_out()
-        except FptaError:
-            R = 0  # no block: the library's state error follows
-        out = np.empty((self.batch_info()["n_psr"], have, R))
+        out = np.empty((self.batch_info()["n_psr"], have, self._block_real()))
         self._check(_lib.fpta_batch_fit(self._h, _ptr(out)), "fpta_batch_fit")
         return out
 
@@ -677,54 +697,32 @@ class Context:
                          rcond=None):
         """The Fourier coefficients of every row of res [n_vec, n_toa] or [n_toa] for any array
         (fpta_fit_coefficients). Returns (coef [P, K, n_vec], kept Fourier columns [P], kept mask [P, K] bool)."""
-        offs = np.ascontiguousarray(offs, dtype=np.int64)
-        if offs.ndim != 1 or len(offs) < 1:
-            raise ValueError("fit_coefficients: offs must be [P + 1]")
-        P, n = len(offs) - 1, int(offs[-1])
-        toas, nu, res = _f64(toas), _f64(nu), _f64(res)
-        if toas.shape != (n,) or nu.shape != (n,):
-            raise ValueError(f"fit_coefficients: toas and nu must hold {n} values")
-        if res.ndim not in (1, 2) or res.shape[-1] != n:
-            raise ValueError(f"fit_coefficients: res must be [n_vec, {n}] or [{n}], got {res.shape}")
-        n_vec = 1 if res.ndim == 1 else res.shape[0]
+        offs, toas, nu, res, P, n, n_vec = self._oneshot_args("fit_coefficients", offs, toas, nu, res)
         n_modes, f, idx, freqf, common = self._fit_args("fit_coefficients", P, n_modes, f, idx, freqf)
-        if M is None:
-            M = np.zeros((n, 0))
-        M, ncol_psr, weights = self._tm_args("fit_coefficients", P, n, M, ncol_psr, weights)
+        M, ncol_psr, weights, rcond = self._tm_args("fit_coefficients", P, n, M, ncol_psr, weights, rcond)
         K = 2 * int(n_modes.sum())
         coef = np.zeros((P, K, n_vec))
         rank, kept = np.zeros(P, dtype=np.int32), np.zeros((P, K), dtype=np.uint8)
         self._check(_lib.fpta_fit_coefficients(self._h, P, _ptr(offs), _ptr(toas), _ptr(nu), len(n_modes),
                                                _ptr(n_modes), _ptr(f), int(common), _ptr(idx), _ptr(freqf),
-                                               M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
-                                               0.0 if rcond is None else float(rcond), n_vec, _ptr(res), _ptr(coef),
-                                               _ptr(rank), _ptr(kept)), "fpta_fit_coefficients")
+                                               M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights), rcond, n_vec,
+                                               _ptr(res), _ptr(coef), _ptr(rank), _ptr(kept)), "fpta_fit_coefficients")
         return coef, rank, kept.astype(bool)
 
-    @staticmethod
-    def _os_args(what, P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G):
+    @classmethod
+    def _os_args(cls, what, P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G):
         """The tables of an optimal-statistic call as contiguous arrays of the C types: the component tables as
         _fit_args makes them (up to OS_MAX_COMP components, OS_MAX_COL columns), phi [P, sum N_c] (a row [sum N_c] is
         repeated), masks None or uint8 [C, n] (an entry None: the component acts everywhere), phi_hat [N_target], G
         [J, P, P]."""
-        n_modes = np.ascontiguousarray(n_modes, dtype=np.int32)
-        if n_modes.ndim != 1 or not 1 <= len(n_modes) <= OS_MAX_COMP or np.any(n_modes < 1):
-            raise ValueError(f"{what}: n_modes must hold 1 .. {OS_MAX_COMP} positive mode counts, got {n_modes}")
+        n_modes, f, idx, freqf, common = cls._fit_args(what, P, n_modes, f, idx, freqf, OS_MAX_COMP, OS_MAX_COL)
         n_f = int(n_modes.sum())
-        if 2 * n_f > OS_MAX_COL:
-            raise ValueError(f"{what}: {2 * n_f} Fourier columns, more than {OS_MAX_COL}")
         target = int(target)
         if not 0 <= target < len(n_modes):
             raise ValueError(f"{what}: target component {target} outside [0, {len(n_modes)})")
         if 2 * int(n_modes[target]) > OS_MAX_COEF:
             raise ValueError(f"{what}: the target has {2 * int(n_modes[target])} Fourier columns, more than "
                              f"{OS_MAX_COEF}")
-        f = _f64(f)
-        if f.shape not in ((n_f,), (P, n_f)):
-            raise ValueError(f"{what}: f must be [{n_f}] or [{P}, {n_f}], got {f.shape}")
-        idx, freqf = _f64(idx), _f64(freqf)
-        if idx.shape != n_modes.shape or freqf.shape != n_modes.shape:
-            raise ValueError(f"{what}: idx and freqf must hold one value per component")
         phi = _f64(phi)
         if phi.shape == (n_f,):
             phi = np.ascontiguousarray(np.tile(phi, (P, 1)))
@@ -749,7 +747,7 @@ class Context:
             G = G[None]
         if G.ndim != 3 or G.shape[1:] != (P, P):
             raise ValueError(f"{what}: G must be [J, {P}, {P}], got {G.shape}")
-        return n_modes, f, idx, freqf, f.ndim == 1, phi, mask, target, phi_hat, np.ascontiguousarray(G)
+        return n_modes, f, idx, freqf, common, phi, mask, target, phi_hat, np.ascontiguousarray(G)
 
     def batch_set_os(self, n_modes, f, idx, freqf, phi, target, phi_hat, G, masks=None, M=None, ncol_psr=None,
                      weights=None, rcond=None):
@@ -766,32 +764,23 @@ class Context:
             return rank, np.zeros((P, P))
         n_modes, f, idx, freqf, common, phi, mask, target, phi_hat, G = self._os_args(
             "batch_set_os", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G)
-        if M is None:
-            M = np.zeros((n, 0))
-        M, ncol_psr, weights = self._tm_args("batch_set_os", P, n, M, ncol_psr, weights)
+        M, ncol_psr, weights, rcond = self._tm_args("batch_set_os", P, n, M, ncol_psr, weights, rcond)
         nab = np.zeros((P, P))
         self._check(_lib.fpta_batch_set_os(self._h, len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx),
                                            _ptr(freqf), _ptr(phi), _ptr(mask), target, _ptr(phi_hat), M.shape[1],
-                                           _ptr(M), _ptr(ncol_psr), _ptr(weights),
-                                           0.0 if rcond is None else float(rcond), len(G), _ptr(G), _ptr(rank),
+                                           _ptr(M), _ptr(ncol_psr), _ptr(weights), rcond, len(G), _ptr(G), _ptr(rank),
                                            _ptr(nab)), "fpta_batch_set_os")
         return rank, nab
 
     def batch_os_info(self):
         """K, N and J of the optimal statistic that is set (0: none) and the realizations of the last result
         (fpta_batch_os_info)."""
-        info = np.zeros(4, dtype=np.int64)
-        self._check(_lib.fpta_batch_os_info(self._h, _ptr(info)), "fpta_batch_os_info")
-        return dict(K=int(info[0]), N=int(info[1]), J=int(info[2]), n_real=int(info[3]))
+        return dict(zip(("K", "N", "J", "n_real"), self._info4(_lib.fpta_batch_os_info, "fpta_batch_os_info")))
 
     def batch_os(self, per_mode=False, coefficients=False):
         """The optimal statistic of the last block (fpta_batch_os): (Q [J, R], Q_mode [J, N, R] or None, X [P, K, R] or
         None). The buffers are sized from the library's own K, N and J."""
-        have = self.batch_os_info()
-        try:
-            _, _, R = self.batch_device_out()
-        except FptaError:
-            R = 0  # no block: the library's state error follows
+        have, R = self.batch_os_info(), self._block_real()
         Q = np.empty((have["J"], R))
         Qm = np.empty((have["J"], have["N"], R)) if per_mode else None
         X = np.empty((self.batch_info()["n_psr"], have["K"], R)) if coefficients else None
@@ -802,29 +791,18 @@ class Context:
                      ncol_psr=None, weights=None, rcond=None):
         """The optimal statistic of every row of res [n_vec, n_toa] or [n_toa] for any array (fpta_os_statistic).
         Returns (Q [J, n_vec], Q_mode [J, N, n_vec], X [P, K, n_vec], kept columns of M [P], N_ab [P, P])."""
-        offs = np.ascontiguousarray(offs, dtype=np.int64)
-        if offs.ndim != 1 or len(offs) < 1:
-            raise ValueError("os_statistic: offs must be [P + 1]")
-        P, n = len(offs) - 1, int(offs[-1])
-        toas, nu, res = _f64(toas), _f64(nu), _f64(res)
-        if toas.shape != (n,) or nu.shape != (n,):
-            raise ValueError(f"os_statistic: toas and nu must hold {n} values")
-        if res.ndim not in (1, 2) or res.shape[-1] != n:
-            raise ValueError(f"os_statistic: res must be [n_vec, {n}] or [{n}], got {res.shape}")
-        n_vec = 1 if res.ndim == 1 else res.shape[0]
+        offs, toas, nu, res, P, n, n_vec = self._oneshot_args("os_statistic", offs, toas, nu, res)
         n_modes, f, idx, freqf, common, phi, mask, target, phi_hat, G = self._os_args(
             "os_statistic", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G)
-        if M is None:
-            M = np.zeros((n, 0))
-        M, ncol_psr, weights = self._tm_args("os_statistic", P, n, M, ncol_psr, weights)
+        M, ncol_psr, weights, rcond = self._tm_args("os_statistic", P, n, M, ncol_psr, weights, rcond)
         N = int(n_modes[target])
         Q, Qm, X = np.zeros((len(G), n_vec)), np.zeros((len(G), N, n_vec)), np.zeros((P, 2 * N, n_vec))
         rank, nab = np.zeros(P, dtype=np.int32), np.zeros((P, P))
         self._check(_lib.fpta_os_statistic(self._h, P, _ptr(offs), _ptr(toas), _ptr(nu), len(n_modes), _ptr(n_modes),
                                            _ptr(f), int(common), _ptr(idx), _ptr(freqf), _ptr(phi), _ptr(mask), target,
-                                           _ptr(phi_hat), M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
-                                           0.0 if rcond is None else float(rcond), len(G), _ptr(G), n_vec, _ptr(res),
-                                           _ptr(Q), _ptr(Qm), _ptr(X), _ptr(rank), _ptr(nab)), "fpta_os_statistic")
+                                           _ptr(phi_hat), M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights), rcond,
+                                           len(G), _ptr(G), n_vec, _ptr(res), _ptr(Q), _ptr(Qm), _ptr(X), _ptr(rank),
+                                           _ptr(nab)), "fpta_os_statistic")
         return Q, Qm, X, rank, nab
 
     @classmethod
@@ -861,31 +839,23 @@ class Context:
             return rank, np.zeros((P, 0))
         n_modes, f, idx, freqf, common, phi, mask, target, phi_grid = self._lnl_args(
             "batch_set_lnl", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_grid)
-        if M is None:
-            M = np.zeros((n, 0))
-        M, ncol_psr, weights = self._tm_args("batch_set_lnl", P, n, M, ncol_psr, weights)
+        M, ncol_psr, weights, rcond = self._tm_args("batch_set_lnl", P, n, M, ncol_psr, weights, rcond)
         ld = np.zeros((P, len(phi_grid)))
         self._check(_lib.fpta_batch_set_lnl(self._h, len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx),
                                             _ptr(freqf), _ptr(phi), _ptr(mask), target, M.shape[1], _ptr(M),
-                                            _ptr(ncol_psr), _ptr(weights), 0.0 if rcond is None else float(rcond),
-                                            len(phi_grid), _ptr(phi_grid), _ptr(rank), _ptr(ld)), "fpta_batch_set_lnl")
+                                            _ptr(ncol_psr), _ptr(weights), rcond, len(phi_grid), _ptr(phi_grid),
+                                            _ptr(rank), _ptr(ld)), "fpta_batch_set_lnl")
         return rank, ld
 
     def batch_lnl_info(self):
         """K, N and G of the likelihood grid that is set (0: none) and the realizations of the last result
         (fpta_batch_lnl_info)."""
-        info = np.zeros(4, dtype=np.int64)
-        self._check(_lib.fpta_batch_lnl_info(self._h, _ptr(info)), "fpta_batch_lnl_info")
-        return dict(K=int(info[0]), N=int(info[1]), G=int(info[2]), n_real=int(info[3]))
+        return dict(zip(("K", "N", "G", "n_real"), self._info4(_lib.fpta_batch_lnl_info, "fpta_batch_lnl_info")))
 
     def batch_lnl(self, per_pulsar=False, coefficients=False):
         """The likelihood grid of the last block (fpta_batch_lnl): (dlnL [G, R], q_psr [P, G, R] or None, X [P, K, R] or
         None). The buffers are sized from the library's own K and G."""
-        have = self.batch_lnl_info()
-        try:
-            _, _, R = self.batch_device_out()
-        except FptaError:
-            R = 0  # no block: the library's state error follows
+        have, R = self.batch_lnl_info(), self._block_real()
         P = self.batch_info()["n_psr"]
         d = np.empty((have["G"], R))
         q = np.empty((P, have["G"], R)) if per_pulsar else None
@@ -898,30 +868,19 @@ class Context:
         """The likelihood grid of every row of res [n_vec, n_toa] or [n_toa] for any array (fpta_lnl_grid). Returns
         (dlnL [G, n_vec], q_psr [P, G, n_vec], X [P, K, n_vec], kept columns of M [P], ld [P, G], U [P, G, K, K] (the
         plan's fp64 factors) or None)."""
-        offs = np.ascontiguousarray(offs, dtype=np.int64)
-        if offs.ndim != 1 or len(offs) < 1:
-            raise ValueError("lnl_grid: offs must be [P + 1]")
-        P, n = len(offs) - 1, int(offs[-1])
-        toas, nu, res = _f64(toas), _f64(nu), _f64(res)
-        if toas.shape != (n,) or nu.shape != (n,):
-            raise ValueError(f"lnl_grid: toas and nu must hold {n} values")
-        if res.ndim not in (1, 2) or res.shape[-1] != n:
-            raise ValueError(f"lnl_grid: res must be [n_vec, {n}] or [{n}], got {res.shape}")
-        n_vec = 1 if res.ndim == 1 else res.shape[0]
+        offs, toas, nu, res, P, n, n_vec = self._oneshot_args("lnl_grid", offs, toas, nu, res)
         n_modes, f, idx, freqf, common, phi, mask, target, phi_grid = self._lnl_args(
             "lnl_grid", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_grid)
-        if M is None:
-            M = np.zeros((n, 0))
-        M, ncol_psr, weights = self._tm_args("lnl_grid", P, n, M, ncol_psr, weights)
+        M, ncol_psr, weights, rcond = self._tm_args("lnl_grid", P, n, M, ncol_psr, weights, rcond)
         K, G = 2 * int(n_modes[target]), len(phi_grid)
         d, q, X = np.zeros((G, n_vec)), np.zeros((P, G, n_vec)), np.zeros((P, K, n_vec))
         rank, ld = np.zeros(P, dtype=np.int32), np.zeros((P, G))
         U = np.zeros((P, G, K, K)) if factors else None
         self._check(_lib.fpta_lnl_grid(self._h, P, _ptr(offs), _ptr(toas), _ptr(nu), len(n_modes), _ptr(n_modes),
                                        _ptr(f), int(common), _ptr(idx), _ptr(freqf), _ptr(phi), _ptr(mask), target,
-                                       M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights),
-                                       0.0 if rcond is None else float(rcond), G, _ptr(phi_grid), n_vec, _ptr(res),
-                                       _ptr(d), _ptr(q), _ptr(X), _ptr(rank), _ptr(ld), _ptr(U)), "fpta_lnl_grid")
+                                       M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights), rcond, G, _ptr(phi_grid),
+                                       n_vec, _ptr(res), _ptr(d), _ptr(q), _ptr(X), _ptr(rank), _ptr(ld), _ptr(U)),
+                    "fpta_lnl_grid")
         return d, q, X, rank, ld, U
 
     def batch_clear(self):

@@ -179,18 +179,9 @@ class BatchSimulator:
 
         The weights are diagonal: ECORR is not part of them, and a generalised least-squares fit against a dense
         covariance is out of scope."""
-        if Mmats is None:
-            Mmats = [p.Mmat for p in self.psrs]
-        Mmats = list(Mmats)
-        if len(Mmats) not in (0, len(self.psrs)):
-            raise ValueError(f"set_timing_model: {len(Mmats)} design matrices for {len(self.psrs)} pulsars")
-        if not Mmats:
-            Mmats = [np.zeros((len(p.toas), 0)) for p in self.psrs]
-        for i, (m, p) in enumerate(zip(Mmats, self.psrs)):
-            if np.ndim(m) != 2 or np.shape(m)[0] != len(p.toas):
-                raise ValueError(f"set_timing_model: design matrix of pulsar {i} must be [{len(p.toas)}, n_col], got "
-                                 f"shape {np.shape(m)}")
-        M, ncol = _tm.stack_design(Mmats)
+        # this call's own defaults: None is each pulsar's Mmat, an empty list no column at all
+        Mmats = "tm" if Mmats is None else list(Mmats) or None
+        M, ncol = _tm.design_of(self.psrs, Mmats, "set_timing_model")
         w = _tm.weights_of(self.psrs, weights, self.n_toa)
         self._has_tm = False
         rank = self.ctx.batch_set_timing_model(M, ncol_psr=ncol, weights=w, rcond=rcond)
@@ -287,20 +278,7 @@ class BatchSimulator:
                  False gives every pulsar its own copy (cross_spectrum() then refuses)."""
         tspan = float(np.ptp(self.toas)) if len(self.toas) else 0.0
         n_modes, f, idx, freqf = _fit.resolve_components(components, len(self.psrs), tspan, self.segments, common)
-        if isinstance(Mmats, str):
-            if Mmats != "tm":
-                raise ValueError(f"set_fourier_fit: Mmats must be 'tm', None or a list of matrices, got {Mmats!r}")
-            Mmats = [p.Mmat for p in self.psrs]
-        if Mmats is None:
-            Mmats = [np.zeros((len(p.toas), 0)) for p in self.psrs]
-        Mmats = list(Mmats)
-        if len(Mmats) != len(self.psrs):
-            raise ValueError(f"set_fourier_fit: {len(Mmats)} design matrices for {len(self.psrs)} pulsars")
-        for i, (m, p) in enumerate(zip(Mmats, self.psrs)):
-            if np.ndim(m) != 2 or np.shape(m)[0] != len(p.toas):
-                raise ValueError(f"set_fourier_fit: design matrix of pulsar {i} must be [{len(p.toas)}, n_col], got "
-                                 f"shape {np.shape(m)}")
-        M, ncol = _tm.stack_design(Mmats)
+        M, ncol = _tm.design_of(self.psrs, Mmats, "set_fourier_fit")
         w = _tm.weights_of(self.psrs, weights, self.n_toa)
         self._fit = None
         rank, kept = self.ctx.batch_set_fit(n_modes, f, idx, freqf, M=M, ncol_psr=ncol, weights=w, rcond=rcond)

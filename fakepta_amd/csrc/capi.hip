@@ -48,6 +48,51 @@ int upload(fpta_ctx* c, DevBuf& buf, const void* src, size_t bytes, const char* 
   return FPTA_OK;
 }
 
+int block_check(fpta_ctx* c, const char* who, bool inject, Block& b) {
+  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
+  const std::string w(who);
+  if (inject && c->batch.P <= 0) return fail(c, FPTA_ESTATE, w + ": set_toas first");
+  if (!c->out_R) return fail(c, FPTA_ESTATE, w + ": nothing synthesized yet");
+  if (inject && c->batch.n_toa > c->out_ld) return fail(c, FPTA_ESTATE, w + ": the block is narrower than the layout");
+  b = Block{c->out.as<double>(), c->out_ld, c->out_R, c->batch.P};
+  return FPTA_OK;
+}
+
+int block_open(fpta_ctx* c, bool writes) {
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  const int rc = join_red(c);
+  if (rc) return rc;
+  if (writes) c->part_ready = false;  // (a reader leaves part_ready and the next-block mix as they are)
+  return FPTA_OK;
+}
+
+int OneShot::check() const {
+  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
+  if (n_psr < 0 || n_vec < 0 || (n_psr > 0 && !offs)) return fail(c, FPTA_EINVAL, std::string(who) + ": bad arguments");
+  return FPTA_OK;
+}
+
+int OneShot::planned(int made, const std::string& why) const {
+  if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, std::string(who) + ": " + why);
+  if (n_vec > 0 && n_toa() > 0 && !res) return fail(c, FPTA_EINVAL, std::string(who) + ": res missing");
+  return FPTA_OK;
+}
+
+int OneShot::upload(Block& b) const {
+  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
+  const int rc = capi::upload(c, c->res1, res, sizeof(double) * (size_t)n_vec * (size_t)n_toa(),
+                              (std::string(who) + " residuals").c_str());
+  if (rc) return rc;
+  b = Block{c->res1.as<double>(), n_toa(), n_vec, n_psr};
+  return FPTA_OK;
+}
+
+int OneShot::done() const {
+  const std::string what = std::string(who) + " sync";
+  HIPCHK(c, hipStreamSynchronize(c->stream), what.c_str());
+  return FPTA_OK;
+}
+
 int layout_set_toas(fpta_ctx* c, Layout& L, int32_t P, const int64_t* offs, const double* toas,
                     const double* nu) {
   if (P <= 0 || !offs || !toas || !nu) return fail(c, FPTA_EINVAL, "set_toas: bad arguments");
@@ -1368,13 +1413,7 @@ int fpta_batch_set_toas(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const d
   if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   c->has_sigma = c->has_blocks = false;
-  c->has_tm = false;  // the timing model's tables are per TOA of the layout they were set for
-  c->has_fit = false;  // and so are the Fourier fit's operators; its last result goes with them
-  c->fit_R = 0;
-  c->has_os = false;  // the optimal statistic's operators too
-  c->os_R = 0;
-  c->has_lnl = false;  // and the likelihood grid's
-  c->lnl_R = 0;
+  c->clear_consumers();
   c->out_R = 0;
   return layout_set_toas(c, c->batch, n_psr, offs, toas, nu);
 }

@@ -169,6 +169,62 @@ struct Layout {
   }
 };
 
+// The consumers of the block that fpta_batch_synth leaves on the device (tm.hip, fit.hip, os.hip, lnl.hip). A slot owns
+// the device tables and results of one feature: the context holds one for the batch layout and one for the feature's
+// one-shot call. A state says what the batch slot holds (set: the feature is set; R, rpad: the realizations of its last
+// result, 0: none, and their padding); it is all zero while the feature is not set, and fpta_batch_set_toas clears it.
+
+// A block [R][ld] of residuals on the device, rows of n_psr pulsars: the resident block, or a one-shot call's upload
+struct Block {
+  double* res = nullptr;
+  int64_t ld = 0;
+  int32_t R = 0, n_psr = 0;
+};
+
+// Timing-model projection: the basis Q [n_toa][16], s = sqrt(w), CSR offsets and ranks
+struct TmSlot {
+  DevBuf q, s, offs, rank;
+};
+struct TmState {
+  bool set = false;
+  void clear() { *this = TmState(); }
+};
+
+// The operator slot k_fit_apply runs on: pulsar p's operator [K][n_p] at K offs[p], CSR offsets, the rows to make per
+// pulsar (the Fourier fit: its kept-column counts; 0 skips the pulsar) and the coefficients [P][K][rpad]
+struct FitSlot {
+  DevBuf a, offs, rows, coef;
+};
+struct FitState {
+  bool set = false, common = false;  // common: one frequency grid for the array
+  int32_t K = 0, modes = 0, R = 0, rpad = 0;
+  void clear() { *this = FitState(); }
+};
+
+// Optimal statistic: k_fit_apply's second operator slot (B_p, X), the template phi_hat [N], the J pair-weight matrices
+// [J][P][P] and the results Q_mode [J][N][rpad], Q [J][rpad]
+struct OsSlot {
+  FitSlot x;
+  DevBuf phi, g, qm, q;
+};
+struct OsState {
+  bool set = false;
+  int32_t K = 0, N = 0, J = 0, R = 0, rpad = 0;  // K = 2 N: the target's Fourier columns
+  void clear() { *this = OsState(); }
+};
+
+// Likelihood grid: k_fit_apply's third operator slot (B_p with the target left out of the model, X), the factors U
+// [P][G][u_stride] (lnl_host.h's layout), the log-determinants [P][G] and the results q [P][G][rpad], dlnL [G][rpad]
+struct LnlSlot {
+  FitSlot x;
+  DevBuf u, ld, q, d;
+};
+struct LnlState {
+  bool set = false;
+  int32_t K = 0, N = 0, G = 0, R = 0, rpad = 0;  // K = 2 N: the target's Fourier columns
+  void clear() { *this = LnlState(); }
+};
+
 }  // namespace capi
 
 using namespace capi;
@@ -205,34 +261,27 @@ struct fpta_ctx {
   // one launch, the ORFs of one launch
   DevBuf orf_pos, orf_rings, orf_h, orf_part, orf_out;
   int64_t orf_split = 0;  // FPTA_OPT_ORF_SPLIT: 0 auto (fpta_orf::make_plan), n >= 1 forces n K-splits
-  // timing-model projection (tm.hip): the batch layout's basis Q [n_toa][16], s = sqrt(w), CSR offsets and ranks
-  // (fpta_batch_set_timing_model; has_tm: a model is set), and the same tables plus the residuals of one
-  // fpta_tm_project call
-  DevBuf tm_q, tm_s, tm_offs, tm_rank, tm1_q, tm1_s, tm1_offs, tm1_rank, tm1_res;
-  bool has_tm = false;
-  // Fourier fit (fit.hip): the batch layout's operators (pulsar p's A_p [K][n_p] at K offs[p]), CSR offsets, kept-column
-  // counts and the cosine / sine row of every mode (fpta_batch_set_fit; has_fit: a fit is set), the coefficients
-  // [P][K][fit_rpad] of the last fpta_batch_fit (fit_R realizations; 0: none) and the cross-spectra of one
-  // fpta_batch_fit_cross; the same tables plus the residuals and coefficients of one fpta_fit_coefficients call
-  DevBuf fit_a, fit_offs, fit_rank, fit_rows, fit_coef, fit_x, fit1_a, fit1_offs, fit1_rank, fit1_res, fit1_coef;
-  bool has_fit = false, fit_common = false;
-  int32_t fit_K = 0, fit_modes = 0, fit_R = 0, fit_rpad = 0;
-  // Optimal statistic (os.hip): k_fit_apply's second operator slot (pulsar p's B_p [K][n_p] at K offs[p], CSR offsets,
-  // the rows to make per pulsar) and coefficient buffer X [P][K][os_rpad], the template phi_hat [N], the J pair-weight
-  // matrices [J][P][P] and the results Q_mode [J][N][os_rpad], Q [J][os_rpad] of the last fpta_batch_os (os_R
-  // realizations; 0: none); the same tables plus the residuals of one fpta_os_statistic call
-  DevBuf os_a, os_offs, os_rows, os_coef, os_phi, os_g, os_qm, os_q;
-  DevBuf os1_a, os1_offs, os1_rows, os1_res, os1_coef, os1_phi, os1_g, os1_qm, os1_q;
-  bool has_os = false;
-  int32_t os_K = 0, os_N = 0, os_J = 0, os_R = 0, os_rpad = 0;
-  // Likelihood grid (lnl.hip): k_fit_apply's third operator slot (B_p with the target left out of the model, CSR
-  // offsets, the rows to make per pulsar) and coefficient buffer X [P][K][lnl_rpad], the factors U [P][G][u_stride]
-  // (lnl_host.h's layout), the log-determinants [P][G] and the results q [P][G][lnl_rpad], dlnL [G][lnl_rpad] of the
-  // last fpta_batch_lnl (lnl_R realizations; 0: none); the same tables plus the residuals of one fpta_lnl_grid call
-  DevBuf lnl_a, lnl_offs, lnl_rows, lnl_coef, lnl_u, lnl_ld, lnl_q, lnl_d;
-  DevBuf lnl1_a, lnl1_offs, lnl1_rows, lnl1_res, lnl1_coef, lnl1_u, lnl1_ld, lnl1_q, lnl1_d;
-  bool has_lnl = false;
-  int32_t lnl_K = 0, lnl_N = 0, lnl_G = 0, lnl_R = 0, lnl_rpad = 0;
+  // The consumers of the resident block, each with the slot of the batch layout, the slot of its one-shot call and the
+  // state of the former: the timing-model projection (tm.hip), the Fourier fit (fit.hip; cross_rows the cosine / sine
+  // row of every mode and cross_x the cross-spectra of one fpta_batch_fit_cross), the optimal statistic (os.hip) and
+  // the likelihood grid (lnl.hip). res1: the residuals of a one-shot call, which ends with the stream idle.
+  TmSlot tm, tm1;
+  TmState tm_st;
+  FitSlot fit, fit1;
+  FitState fit_st;
+  DevBuf cross_rows, cross_x;
+  OsSlot os, os1;
+  OsState os_st;
+  LnlSlot lnl, lnl1;
+  LnlState lnl_st;
+  DevBuf res1;
+  // a new layout: every table above is per TOA of the layout it was set for, and the last results go with them
+  void clear_consumers() {
+    tm_st.clear();
+    fit_st.clear();
+    os_st.clear();
+    lnl_st.clear();
+  }
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
   int32_t out_R = 0;
@@ -457,14 +506,48 @@ int batch_common(fpta_ctx* c, uint64_t seed, int64_t real0, int32_t n_real, cons
 int launch_block_checksums(fpta_ctx* c, bool async = false, hipStream_t* used = nullptr, double* dst = nullptr,
                            bool* direct = nullptr);
 
-// fit.hip: k_fit_apply on any operator slot (coef [n_psr][K][R_pad] = A_p r, cleared first; rank[p] == 0: the pulsar
-// is skipped), and the download of such a buffer as [rows][R]. fit_launch books one FPTA_K_DENSE entry;
-// fit_launch_unbooked none (the caller's KTimer spans it).
-int fit_launch_unbooked(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K,
-                        const DevBuf& A, const DevBuf& offs, const DevBuf& rank, DevBuf& coef, int32_t& R_pad);
-int fit_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K, const DevBuf& A,
-               const DevBuf& offs, const DevBuf& rank, DevBuf& coef, int32_t& R_pad);
+// The opening of a call on the resident block, `who` the prefix of its messages. block_check refuses a null context,
+// for an injection a context without a layout ("set_toas first"), a context without a block ("nothing synthesized
+// yet") and for an injection a block narrower than the layout, in that order, and gives the block. block_open, after
+// the caller's own refusals: the device, the join of a streamed job's reductions, which may still run beside the ctx
+// stream, and for a call that writes the block the end of the interpolation's partial checksums, which describe the
+// block as it was.
+int block_check(fpta_ctx* c, const char* who, bool inject, Block& b);
+int block_open(fpta_ctx* c, bool writes);
+
+// The frame of a one-shot call on any array: n_vec residual vectors [n_vec][n_toa] of n_psr pulsars, `who` the prefix
+// of its messages. Between the steps the call makes its own plan, copies its own tables out and returns early where
+// there is nothing to launch.
+struct OneShot {
+  fpta_ctx* c;
+  const char* who;
+  int32_t n_psr;
+  const int64_t* offs;
+  int32_t n_vec;
+  const double* res;
+  int64_t n_toa() const { return n_psr > 0 ? offs[n_psr] : 0; }
+  int check() const;  // a null context, "bad arguments"
+  // the plan's outcome (0 made, 1 refused for the reason why, 2 out of host memory), then "res missing"
+  int planned(int made, const std::string& why) const;
+  int upload(Block& b) const;  // the device, and the residuals into c->res1
+  int done() const;            // the stream has run: the residuals' upload is done with its source
+};
+
+// fit.hip: k_fit_apply on any operator slot (coef [n_psr][K][R_pad] = A_p r, cleared first; rows[p] == 0: the pulsar
+// is skipped), the upload of such a slot's operator, offsets and rows (the caller syncs before it where a previous
+// launch may still read them), and the download of a buffer [rows][R_pad] as [rows][R]. fit_launch books one
+// FPTA_K_DENSE entry; fit_launch_unbooked none (the caller's KTimer spans it).
+int fit_launch_unbooked(fpta_ctx* c, const Block& b, int32_t K, FitSlot& s, int32_t& R_pad);
+int fit_launch(fpta_ctx* c, const Block& b, int32_t K, FitSlot& s, int32_t& R_pad);
+int fit_upload(fpta_ctx* c, const char* who, FitSlot& s, int32_t K, const std::vector<double>& A, int32_t n_psr,
+               const int64_t* offs, const std::vector<int32_t>& rows);
 int fit_download(fpta_ctx* c, const DevBuf& coef, int64_t rows, int32_t R, int32_t R_pad, double* host);
+
+// cw_batch.hip: the one-table mode of an injection, every realization of the block getting the same delay vector.
+// bcast_vector sizes v [n_toa of the batch layout] and clears it; the caller's drop-in kernel fills it; bcast_add
+// then runs k_cw_bcast, block[r][i] += v[i]. Neither books a timer entry: the caller's spans its kernel and the add.
+int bcast_vector(fpta_ctx* c, const char* who, DevBuf& v);
+int bcast_add(fpta_ctx* c, const char* who, const DevBuf& v, const Block& b);
 
 // grid_host.hip
 constexpr double kGridAutoRatio = 0.5;  // auto path: gridded when it needs < half the direct FMAs

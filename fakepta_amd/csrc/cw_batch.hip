@@ -93,19 +93,38 @@ __global__ __launch_bounds__(256) void k_cw_bcast(const double* __restrict__ v, 
   for (int32_t r = r0; r < r1; ++r) block[(int64_t)r * ld + i] += x;
 }
 
+int bcast_vector(fpta_ctx* c, const char* who, DevBuf& v) {
+  const std::string what = std::string(who) + " delay vector";
+  const size_t bytes = sizeof(double) * (size_t)c->batch.n_toa;
+  HIPCHK(c, v.ensure(bytes), what.c_str());
+  HIPCHK(c, hipMemsetAsync(v.p, 0, bytes, c->stream), what.c_str());
+  return FPTA_OK;
+}
+
+int bcast_add(fpta_ctx* c, const char* who, const DevBuf& v, const Block& b) {
+  const int64_t n_toa = c->batch.n_toa;
+  const int64_t n_chunk = (n_toa + 255) / 256, n_rg = ((int64_t)b.R + kCwbRows - 1) / kCwbRows;
+  // (a block that large, 32 TB, fits no device: the refusal only guards the grid's arithmetic)
+  if (n_chunk * n_rg > 0x7FFFFFFF) return fail(c, FPTA_EINVAL, std::string(who) + ": block too large");
+  k_cw_bcast<<<dim3((unsigned)(n_chunk * n_rg)), dim3(256), 0, c->stream>>>(v.as<double>(), n_toa, (uint32_t)n_chunk,
+                                                                           b.R, b.ld, b.res);
+  HIPCHK(c, hipGetLastError(), "k_cw_bcast launch");
+  return FPTA_OK;
+}
+
 }  // namespace capi
 
 using namespace capi;
 
 extern "C" int fpta_batch_cw_accumulate(fpta_ctx* c, const double* pos, const double* pdist_s, int64_t pdist_stride,
                                         int32_t n_tab, const int64_t* src_offs, const double* src, double sign) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
+  const char* who = "batch_cw_accumulate";
+  Block b;
+  int rc;
+  if ((rc = block_check(c, who, true, b))) return rc;
   const Layout& L = c->batch;
-  if (L.P <= 0) return fail(c, FPTA_ESTATE, "batch_cw_accumulate: set_toas first");
-  if (!c->out_R) return fail(c, FPTA_ESTATE, "batch_cw_accumulate: nothing synthesized yet");
-  const int32_t R = c->out_R;
-  const int64_t ld = c->out_ld, n_toa = L.n_toa;
-  if (n_toa > ld) return fail(c, FPTA_ESTATE, "batch_cw_accumulate: the block is narrower than the layout");
+  const int32_t R = b.R;
+  const int64_t n_toa = L.n_toa;
   // everything is validated and the per-source constants made here, before anything is uploaded or launched
   double tmax = L.h_toas[0];
   for (int64_t i = 1; i < n_toa; ++i) tmax = std::max(tmax, L.h_toas[(size_t)i]);
@@ -117,30 +136,21 @@ extern "C" int fpta_batch_cw_accumulate(fpta_ctx* c, const double* pos, const do
   if (plan.n_src == 0) return FPTA_OK;  // the block, and what is known about it, stay as they are
   const bool shared = n_tab == 1 && pdist_stride == 0;  // every realization gets the same delay vector
   const int64_t n_slab = (int64_t)plan.slabs.size();
-  const int64_t n_chunk = (n_toa + 255) / 256, n_rg = ((int64_t)R + kCwbRows - 1) / kCwbRows;
   if (shared) {
     if (plan.n_src > 0x7FFFFFFF || (int64_t)L.P * plan.n_src > (int64_t)1 << 31)
       return fail(c, FPTA_EINVAL, "batch_cw_accumulate: more than 2^31 (pulsar, source) pairs");
-    if (n_chunk * n_rg > 0x7FFFFFFF) return fail(c, FPTA_EINVAL, "batch_cw_accumulate: block too large");
   } else if (n_slab * R > 0x7FFFFFFF) {
     return fail(c, FPTA_EINVAL, "batch_cw_accumulate: too many TOA slabs x realizations");
   }
 
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc = join_red(c);  // a streamed job's reductions may still run beside the ctx stream
-  if (rc) return rc;
-  c->part_ready = false;  // the interpolation's partial checksums describe the block before the injection
-  double* block = c->out.as<double>();
+  if ((rc = block_open(c, true))) return rc;
   CwRun run;  // (its wave table lives until the sync below)
   if (shared) {
     if ((rc = cw_prepare(c, L.P, L.h_offs.data(), pos, pdist_s, plan.ev, plan.gm, run))) return rc;
-    HIPCHK(c, c->cwb_v.ensure(sizeof(double) * (size_t)n_toa), "cw batch delay vector");
-    HIPCHK(c, hipMemsetAsync(c->cwb_v.p, 0, sizeof(double) * (size_t)n_toa, c->stream), "cw batch delay vector clear");
+    if ((rc = bcast_vector(c, who, c->cwb_v))) return rc;
     KTimer kt(c, FPTA_K_CW);
     if ((rc = cw_launch(c, run, L.toas.as<double>(), sign, c->cwb_v.as<double>()))) return rc;
-    k_cw_bcast<<<dim3((unsigned)(n_chunk * n_rg)), dim3(256), 0, c->stream>>>(c->cwb_v.as<double>(), n_toa,
-                                                                             (uint32_t)n_chunk, R, ld, block);
-    HIPCHK(c, hipGetLastError(), "k_cw_bcast launch");
+    if ((rc = bcast_add(c, who, c->cwb_v, b))) return rc;
   } else {
     const size_t n_dist = pdist_stride ? (size_t)R * (size_t)L.P : (size_t)L.P;
     if ((rc = upload(c, c->cwb_pos, pos, sizeof(double) * 3 * (size_t)L.P, "cw batch pos"))) return rc;
@@ -154,7 +164,7 @@ extern "C" int fpta_batch_cw_accumulate(fpta_ctx* c, const double* pos, const do
     k_cw_block<<<dim3((unsigned)(n_slab * R)), dim3(kCwbThreads), 0, c->stream>>>(
         c->cwb_slabs.as<Slab>(), (uint32_t)n_slab, L.toas.as<double>(), n_toa, c->cwb_pos.as<double>(),
         c->cwb_L.as<double>(), pdist_stride, c->cwb_offs.as<int64_t>(), n_tab == 1 ? 0 : 1, c->cwb_ev.as<SrcEval>(),
-        c->cwb_gm.as<SrcGeom>(), sign, R, ld, block);
+        c->cwb_gm.as<SrcGeom>(), sign, R, b.ld, b.res);
     HIPCHK(c, hipGetLastError(), "k_cw_block launch");
   }
   // the tables above are this call's own host memory: the stream has taken them once it has run

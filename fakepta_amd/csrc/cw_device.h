@@ -73,11 +73,8 @@ int cw_prepare(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const double* po
                const std::vector<SrcEval>& ev, const std::vector<SrcGeom>& gm, CwRun& r);
 int cw_launch(fpta_ctx* c, const CwRun& r, const double* toas, double sign, double* res);
 
-// cw_batch.hip: block[r][i] += v[i] for every realization r < n_real and column i < n_toa, each thread adding its
-// column's v to kCwbRows rows. Grid: ceil(n_real / kCwbRows) x n_chunk workgroups of 256 threads in x, n_chunk =
-// ceil(n_toa / 256), the column chunk fastest. roemer_batch.hip launches it too.
+// cw_batch.hip: the rows of the block each thread of k_cw_bcast adds its column's value to (bcast_add launches it, for
+// roemer_batch.hip too)
 constexpr int kCwbRows = 8;
-__global__ __launch_bounds__(256) void k_cw_bcast(const double* __restrict__ v, int64_t n_toa, uint32_t n_chunk,
-                                                   int32_t n_real, int64_t ld, double* __restrict__ block);
 
 }  // namespace capi

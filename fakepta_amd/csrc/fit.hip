@@ -226,27 +226,32 @@ __global__ __launch_bounds__(64) void k_fit_cross(CrossArgs a) {
   }
 }
 
-// Clears coef [n_psr][K][R_pad] and runs k_fit_apply on a block [R][ld] against device tables; no FPTA_K_DENSE entry
-int fit_launch_unbooked(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K,
-                        const DevBuf& A, const DevBuf& offs, const DevBuf& rank, DevBuf& coef, int32_t& R_pad) {
-  R_pad = (R + kFitRpad - 1) / kFitRpad * kFitRpad;
-  const size_t bytes = sizeof(double) * (size_t)n_psr * (size_t)K * (size_t)R_pad;
-  if (coef.ensure(bytes) != hipSuccess)
+// What a launch may allocate or refuse: the slot's coefficient buffer [n_psr][K][R_pad] and the grid bound
+static int fit_size(fpta_ctx* c, const Block& b, int32_t K, FitSlot& s, int32_t& R_pad, size_t& bytes) {
+  R_pad = (b.R + kFitRpad - 1) / kFitRpad * kFitRpad;
+  bytes = sizeof(double) * (size_t)b.n_psr * (size_t)K * (size_t)R_pad;
+  if (s.coef.ensure(bytes) != hipSuccess)
     return fail(c, FPTA_ENOMEM, "fit: no device memory for " + std::to_string(bytes) + " bytes of coefficients");
+  if ((int64_t)b.n_psr * ((b.R + kFitReal - 1) / kFitReal) > 0x7FFFFFFF)
+    return fail(c, FPTA_EINVAL, "fit: too many pulsars x realization tiles");
+  return FPTA_OK;
+}
+
+// Clears the sized buffer and runs k_fit_apply on the block against the slot's tables
+static int fit_run(fpta_ctx* c, const Block& b, int32_t K, const FitSlot& s, int32_t R_pad, size_t bytes) {
   FitArgs a;
-  a.res = res;
-  a.ld = ld;
-  a.R = R;
-  a.n_rt = (R + kFitReal - 1) / kFitReal;
+  a.res = b.res;
+  a.ld = b.ld;
+  a.R = b.R;
+  a.n_rt = (b.R + kFitReal - 1) / kFitReal;
   a.K = K;
   a.R_pad = R_pad;
-  a.A = A.as<double>();
-  a.offs = offs.as<int64_t>();
-  a.rank = rank.as<int32_t>();
-  a.coef = coef.as<double>();
-  const int64_t blocks = (int64_t)n_psr * a.n_rt;
-  if (blocks > 0x7FFFFFFF) return fail(c, FPTA_EINVAL, "fit: too many pulsars x realization tiles");
-  HIPCHK(c, hipMemsetAsync(coef.p, 0, bytes, c->stream), "fit coefficients clear");
+  a.A = s.a.as<double>();
+  a.offs = s.offs.as<int64_t>();
+  a.rank = s.rows.as<int32_t>();
+  a.coef = s.coef.as<double>();
+  const int64_t blocks = (int64_t)b.n_psr * a.n_rt;
+  HIPCHK(c, hipMemsetAsync(s.coef.p, 0, bytes, c->stream), "fit coefficients clear");
   if (blocks == 0) return FPTA_OK;
   const dim3 grid((unsigned)blocks), block(64 * kFitWaves);
   if (K <= 16)
@@ -261,29 +266,34 @@ int fit_launch_unbooked(fpta_ctx* c, const double* res, int64_t ld, int32_t R, i
   return FPTA_OK;
 }
 
-// The same with one FPTA_K_DENSE entry around the clear and the launch (the buffer is sized before the entry starts)
-int fit_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K, const DevBuf& A,
-               const DevBuf& offs, const DevBuf& rank, DevBuf& coef, int32_t& R_pad) {
-  const size_t bytes = sizeof(double) * (size_t)n_psr * (size_t)K * (size_t)((R + kFitRpad - 1) / kFitRpad * kFitRpad);
-  if (coef.ensure(bytes) != hipSuccess)
-    return fail(c, FPTA_ENOMEM, "fit: no device memory for " + std::to_string(bytes) + " bytes of coefficients");
-  if ((int64_t)n_psr * ((R + kFitReal - 1) / kFitReal) > 0x7FFFFFFF)
-    return fail(c, FPTA_EINVAL, "fit: too many pulsars x realization tiles");
-  KTimer kt(c, FPTA_K_DENSE);
-  return fit_launch_unbooked(c, res, ld, R, n_psr, K, A, offs, rank, coef, R_pad);
+int fit_launch_unbooked(fpta_ctx* c, const Block& b, int32_t K, FitSlot& s, int32_t& R_pad) {
+  size_t bytes = 0;
+  const int rc = fit_size(c, b, K, s, R_pad, bytes);
+  return rc ? rc : fit_run(c, b, K, s, R_pad, bytes);
 }
 
-// Device copies of a plan's tables. The operator is the large one (8 K n_toa bytes): a failed allocation says so.
-static int fit_upload(fpta_ctx* c, const fpta_fit::Plan& plan, int32_t n_psr, const int64_t* offs, DevBuf& A,
-                      DevBuf& d_offs, DevBuf& rank) {
-  const size_t bytes = sizeof(double) * plan.A.size();
-  if (A.ensure(bytes) != hipSuccess)
-    return fail(c, FPTA_ENOMEM, "fit: no device memory for the operator of " + std::to_string(bytes) +
-                                    " bytes (8 K n_toa, K = " + std::to_string(plan.K) + ")");
+// One FPTA_K_DENSE entry around the clear and the launch: the buffer is sized before the entry starts
+int fit_launch(fpta_ctx* c, const Block& b, int32_t K, FitSlot& s, int32_t& R_pad) {
+  size_t bytes = 0;
+  const int rc = fit_size(c, b, K, s, R_pad, bytes);
+  if (rc) return rc;
+  KTimer kt(c, FPTA_K_DENSE);
+  return fit_run(c, b, K, s, R_pad, bytes);
+}
+
+// Device copies of an operator slot's tables. The operator is the large one (8 K n_toa bytes): a failed allocation
+// says so.
+int fit_upload(fpta_ctx* c, const char* who, FitSlot& s, int32_t K, const std::vector<double>& A, int32_t n_psr,
+               const int64_t* offs, const std::vector<int32_t>& rows) {
+  const std::string w(who);
+  const size_t bytes = sizeof(double) * A.size();
+  if (s.a.ensure(bytes) != hipSuccess)
+    return fail(c, FPTA_ENOMEM, w + ": no device memory for the operator of " + std::to_string(bytes) +
+                                    " bytes (8 K n_toa, K = " + std::to_string(K) + ")");
   int rc;
-  if ((rc = upload(c, A, plan.A.data(), bytes, "fit operator"))) return rc;
-  if ((rc = upload(c, d_offs, offs, sizeof(int64_t) * ((size_t)n_psr + 1), "fit offs"))) return rc;
-  if ((rc = upload(c, rank, plan.rank.data(), sizeof(int32_t) * (size_t)n_psr, "fit ranks"))) return rc;
+  if ((rc = upload(c, s.a, A.data(), bytes, (w + " operator").c_str()))) return rc;
+  if ((rc = upload(c, s.offs, offs, sizeof(int64_t) * ((size_t)n_psr + 1), (w + " offs").c_str()))) return rc;
+  if ((rc = upload(c, s.rows, rows.data(), sizeof(int32_t) * (size_t)n_psr, (w + " rows").c_str()))) return rc;
   return FPTA_OK;
 }
 
@@ -295,18 +305,6 @@ int fit_download(fpta_ctx* c, const DevBuf& coef, int64_t rows, int32_t R, int32
            "fit download");
   HIPCHK(c, hipStreamSynchronize(c->stream), "fit sync");
   return FPTA_OK;
-}
-
-static fpta_fit::Spec fit_spec(int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
-                               const double* idx, const double* freqf) {
-  fpta_fit::Spec sp;
-  sp.n_comp = n_comp;
-  sp.n_modes = n_modes;
-  sp.f = f;
-  sp.f_is_common = f_is_common != 0;
-  sp.idx = idx;
-  sp.freqf = freqf;
-  return sp;
 }
 
 }  // namespace capi
@@ -321,37 +319,32 @@ extern "C" int fpta_batch_set_fit(fpta_ctx* c, int32_t n_comp, const int32_t* n_
   const Layout& L = c->batch;
   if (L.P <= 0) return fail(c, FPTA_ESTATE, "set_fit: set_toas first");
   if (n_comp == 0) {
-    c->has_fit = false;
-    c->fit_R = 0;
+    c->fit_st.clear();
     if (rank_out) std::fill(rank_out, rank_out + L.P, 0);
     return FPTA_OK;
   }
   // everything is validated and the operator built here, before anything is uploaded
   std::string why;
   fpta_fit::Plan plan;
-  const fpta_fit::Spec sp = fit_spec(n_comp, n_modes, f, f_is_common, idx, freqf);
+  const fpta_fit::Spec sp = fpta_fit::make_spec(n_comp, n_modes, f, f_is_common, idx, freqf);
   const int made = fpta_fit::make_plan(L.P, L.h_offs.data(), L.h_toas.data(), L.h_nu.data(), sp, n_col, M, ncol_psr,
                                        weights, rcond, plan, why);
   if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, "set_fit: " + why);
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  c->has_fit = false;
-  c->fit_R = 0;
+  c->fit_st.clear();
   // a fit with the previous operator may still read the tables (an upload into a buffer that does not grow)
   HIPCHK(c, hipStreamSynchronize(c->stream), "set_fit sync");
   int rc;
-  if ((rc = fit_upload(c, plan, L.P, L.h_offs.data(), c->fit_a, c->fit_offs, c->fit_rank))) return rc;
+  if ((rc = fit_upload(c, "fit", c->fit, plan.K, plan.A, L.P, L.h_offs.data(), plan.rank))) return rc;
   std::vector<int32_t> rows;
   for (int32_t k0 = 0, ci = 0; ci < n_comp; k0 += 2 * n_modes[ci], ++ci)
     for (int32_t k = 0; k < n_modes[ci]; ++k) {
       rows.push_back(k0 + k);
       rows.push_back(k0 + n_modes[ci] + k);
     }
-  if ((rc = upload(c, c->fit_rows, rows.data(), sizeof(int32_t) * rows.size(), "fit mode rows"))) return rc;
+  if ((rc = upload(c, c->cross_rows, rows.data(), sizeof(int32_t) * rows.size(), "fit mode rows"))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream), "set_fit sync");
-  c->has_fit = true;
-  c->fit_K = plan.K;
-  c->fit_modes = (int32_t)(rows.size() / 2);
-  c->fit_common = sp.f_is_common;
+  c->fit_st = FitState{true, sp.f_is_common, plan.K, (int32_t)(rows.size() / 2)};
   if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
   if (kept_out) std::copy(plan.kept.begin(), plan.kept.end(), kept_out);
   return FPTA_OK;
@@ -359,55 +352,52 @@ extern "C" int fpta_batch_set_fit(fpta_ctx* c, int32_t n_comp, const int32_t* n_
 
 extern "C" int fpta_batch_fit_info(fpta_ctx* c, int64_t* info) {
   if (!c || !info) return fail(c, FPTA_EINVAL, "fit_info: bad arguments");
-  info[0] = c->has_fit ? c->fit_K : 0;
-  info[1] = c->has_fit ? c->fit_modes : 0;
-  info[2] = c->has_fit && c->fit_common ? 1 : 0;
-  info[3] = c->has_fit ? c->fit_R : 0;
+  const FitState& st = c->fit_st;  // all zero while no fit is set
+  const int64_t v[4] = {st.K, st.modes, st.common ? 1 : 0, st.R};
+  std::copy(v, v + 4, info);
   return FPTA_OK;
 }
 
 extern "C" int fpta_batch_fit(fpta_ctx* c, double* coef_host) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (!c->out_R) return fail(c, FPTA_ESTATE, "fit: nothing synthesized yet");
-  if (!c->has_fit) return fail(c, FPTA_ESTATE, "fit: no fit is set (set_fit first)");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc = join_red(c);  // a streamed job's reductions may still run beside the ctx stream
-  if (rc) return rc;
-  c->fit_R = 0;
-  // the block is read only: part_ready and the next-block mix stay as they are
-  if ((rc = fit_launch(c, c->out.as<double>(), c->out_ld, c->out_R, c->batch.P, c->fit_K, c->fit_a, c->fit_offs,
-                       c->fit_rank, c->fit_coef, c->fit_rpad)))
-    return rc;
-  c->fit_R = c->out_R;
-  if (coef_host) return fit_download(c, c->fit_coef, (int64_t)c->batch.P * c->fit_K, c->fit_R, c->fit_rpad, coef_host);
+  Block b;
+  int rc;
+  if ((rc = block_check(c, "fit", false, b))) return rc;
+  FitState& st = c->fit_st;
+  if (!st.set) return fail(c, FPTA_ESTATE, "fit: no fit is set (set_fit first)");
+  if ((rc = block_open(c, false))) return rc;
+  st.R = 0;
+  if ((rc = fit_launch(c, b, st.K, c->fit, st.rpad))) return rc;
+  st.R = b.R;
+  if (coef_host) return fit_download(c, c->fit.coef, (int64_t)b.n_psr * st.K, st.R, st.rpad, coef_host);
   return FPTA_OK;
 }
 
 extern "C" int fpta_batch_fit_cross(fpta_ctx* c, double* out) {
   if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (!c->has_fit || !c->fit_R) return fail(c, FPTA_ESTATE, "fit_cross: no fit result (fpta_batch_fit first)");
-  if (!c->fit_common) return fail(c, FPTA_EINVAL, "fit_cross: the fit has per-pulsar frequencies; a common grid is needed");
+  const FitState& st = c->fit_st;
+  if (!st.set || !st.R) return fail(c, FPTA_ESTATE, "fit_cross: no fit result (fpta_batch_fit first)");
+  if (!st.common) return fail(c, FPTA_EINVAL, "fit_cross: the fit has per-pulsar frequencies; a common grid is needed");
   if (!out) return fail(c, FPTA_EINVAL, "fit_cross: null output");
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   const int32_t P = c->batch.P, n_tile = (P + 15) / 16;
-  const size_t bytes = sizeof(double) * (size_t)c->fit_modes * (size_t)P * (size_t)P;
-  if (c->fit_x.ensure(bytes) != hipSuccess)
+  const size_t bytes = sizeof(double) * (size_t)st.modes * (size_t)P * (size_t)P;
+  if (c->cross_x.ensure(bytes) != hipSuccess)
     return fail(c, FPTA_ENOMEM, "fit_cross: no device memory for " + std::to_string(bytes) + " bytes of cross-spectra");
   CrossArgs a;
-  a.coef = c->fit_coef.as<double>();
+  a.coef = c->fit.coef.as<double>();
   a.P = P;
-  a.K = c->fit_K;
-  a.R_pad = c->fit_rpad;
+  a.K = st.K;
+  a.R_pad = st.rpad;
   a.n_tile = n_tile;
-  a.rows = c->fit_rows.as<int32_t>();
-  a.X = c->fit_x.as<double>();
-  if (c->fit_modes > 65535) return fail(c, FPTA_EINVAL, "fit_cross: too many modes");
+  a.rows = c->cross_rows.as<int32_t>();
+  a.X = c->cross_x.as<double>();
+  if (st.modes > 65535) return fail(c, FPTA_EINVAL, "fit_cross: too many modes");
   {
     KTimer kt(c, FPTA_K_DENSE);
-    k_fit_cross<<<dim3((unsigned)(n_tile * n_tile), (unsigned)c->fit_modes), dim3(64), 0, c->stream>>>(a);
+    k_fit_cross<<<dim3((unsigned)(n_tile * n_tile), (unsigned)st.modes), dim3(64), 0, c->stream>>>(a);
     HIPCHK(c, hipGetLastError(), "k_fit_cross launch");
   }
-  HIPCHK(c, hipMemcpyAsync(out, c->fit_x.p, bytes, hipMemcpyDeviceToHost, c->stream), "fit_cross download");
+  HIPCHK(c, hipMemcpyAsync(out, c->cross_x.p, bytes, hipMemcpyDeviceToHost, c->stream), "fit_cross download");
   HIPCHK(c, hipStreamSynchronize(c->stream), "fit_cross sync");
   return FPTA_OK;
 }
@@ -418,32 +408,27 @@ extern "C" int fpta_fit_coefficients(fpta_ctx* c, int32_t n_psr, const int64_t* 
                                      const double* M, const int32_t* ncol_psr, const double* weights, double rcond,
                                      int32_t n_vec, const double* res, double* coef_out, int32_t* rank_out,
                                      uint8_t* kept_out) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (n_psr < 0 || n_vec < 0 || (n_psr > 0 && !offs)) return fail(c, FPTA_EINVAL, "fit_coefficients: bad arguments");
+  const OneShot one{c, "fit_coefficients", n_psr, offs, n_vec, res};
+  int rc;
+  if ((rc = one.check())) return rc;
   std::string why;
   fpta_fit::Plan plan;
-  const fpta_fit::Spec sp = fit_spec(n_comp, n_modes, f, f_is_common, idx, freqf);
+  const fpta_fit::Spec sp = fpta_fit::make_spec(n_comp, n_modes, f, f_is_common, idx, freqf);
   const int made = fpta_fit::make_plan(n_psr, offs, toas, nu, sp, n_col, M, ncol_psr, weights, rcond, plan, why);
-  if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, "fit_coefficients: " + why);
-  const int64_t n_toa = n_psr > 0 ? offs[n_psr] : 0;
-  if (n_vec > 0 && n_toa > 0 && !res) return fail(c, FPTA_EINVAL, "fit_coefficients: res missing");
+  if ((rc = one.planned(made, why))) return rc;
   if (n_vec > 0 && n_psr > 0 && !coef_out) return fail(c, FPTA_EINVAL, "fit_coefficients: coef_out missing");
   if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
   if (kept_out) std::copy(plan.kept.begin(), plan.kept.end(), kept_out);
   if (n_psr == 0 || n_vec == 0) return FPTA_OK;
   const int64_t rows = (int64_t)n_psr * plan.K;
-  if (n_toa == 0 || plan.max_rank == 0) {  // nothing to launch: every coefficient is zero
+  if (one.n_toa() == 0 || plan.max_rank == 0) {  // nothing to launch: every coefficient is zero
     std::fill(coef_out, coef_out + rows * n_vec, 0.0);
     return FPTA_OK;
   }
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc;
-  if ((rc = fit_upload(c, plan, n_psr, offs, c->fit1_a, c->fit1_offs, c->fit1_rank))) return rc;
-  if ((rc = upload(c, c->fit1_res, res, sizeof(double) * (size_t)n_vec * (size_t)n_toa, "fit_coefficients residuals")))
-    return rc;
+  Block b;
+  if ((rc = one.upload(b))) return rc;
+  if ((rc = fit_upload(c, "fit", c->fit1, plan.K, plan.A, n_psr, offs, plan.rank))) return rc;
   int32_t R_pad = 0;
-  if ((rc = fit_launch(c, c->fit1_res.as<double>(), n_toa, n_vec, n_psr, plan.K, c->fit1_a, c->fit1_offs, c->fit1_rank,
-                       c->fit1_coef, R_pad)))
-    return rc;
-  return fit_download(c, c->fit1_coef, rows, n_vec, R_pad, coef_out);
+  if ((rc = fit_launch(c, b, plan.K, c->fit1, R_pad))) return rc;
+  return fit_download(c, c->fit1.coef, rows, n_vec, R_pad, coef_out);  // its sync closes the call
 }

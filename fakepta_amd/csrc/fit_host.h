@@ -33,6 +33,19 @@ struct Spec {
   const double* freqf = nullptr;  // [n_comp] reference radio frequency
 };
 
+// The component tables as the C entry points pass them
+inline Spec make_spec(int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common, const double* idx,
+                      const double* freqf) {
+  Spec sp;
+  sp.n_comp = n_comp;
+  sp.n_modes = n_modes;
+  sp.f = f;
+  sp.f_is_common = f_is_common != 0;
+  sp.idx = idx;
+  sp.freqf = freqf;
+  return sp;
+}
+
 inline int64_t modes_of(const Spec& sp) {
   int64_t n = 0;
   for (int32_t c = 0; c < sp.n_comp; ++c) n += sp.n_modes[c];

@@ -129,52 +129,28 @@ __global__ __launch_bounds__(256) void k_lnl_reduce(const double* __restrict__ q
   d[e] = s;
 }
 
-// One slot: the device tables of a grid and its results
-struct LnlSlot {
-  DevBuf &a, &offs, &rows, &coef, &u, &ld, &q, &d;
-};
-
-static fpta_os::Spec lnl_spec(int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
-                              const double* idx, const double* freqf, const double* phi, const uint8_t* mask,
-                              int32_t target) {
-  fpta_os::Spec sp;
-  sp.comps.n_comp = n_comp;
-  sp.comps.n_modes = n_modes;
-  sp.comps.f = f;
-  sp.comps.f_is_common = f_is_common != 0;
-  sp.comps.idx = idx;
-  sp.comps.freqf = freqf;
-  sp.phi = phi;
-  sp.mask = mask;
-  sp.target = target;
-  return sp;
-}
-
 // Device copies of a plan's tables. U is the large one (8 P G u_stride bytes), then the operator (8 K n_toa bytes).
-static int lnl_upload(fpta_ctx* c, const fpta_lnl::Plan& plan, int32_t n_psr, const int64_t* offs, const LnlSlot& s) {
-  const size_t b_a = sizeof(double) * plan.B.size(), b_u = sizeof(double) * plan.U.size();
-  if (s.a.ensure(b_a) != hipSuccess || s.u.ensure(b_u) != hipSuccess)
-    return fail(c, FPTA_ENOMEM, "lnl: no device memory for the operator of " + std::to_string(b_a) +
-                                    " bytes (8 K n_toa) and the factors of " + std::to_string(b_u) +
-                                    " bytes (K = " + std::to_string(plan.K) + ", G = " + std::to_string(plan.G) + ")");
+static int lnl_upload(fpta_ctx* c, const fpta_lnl::Plan& plan, int32_t n_psr, const int64_t* offs, LnlSlot& s) {
   int rc;
-  if ((rc = upload(c, s.a, plan.B.data(), b_a, "lnl operator"))) return rc;
+  if ((rc = fit_upload(c, "lnl", s.x, plan.K, plan.B, n_psr, offs, plan.rows))) return rc;
+  const size_t b_u = sizeof(double) * plan.U.size();
+  if (s.u.ensure(b_u) != hipSuccess)
+    return fail(c, FPTA_ENOMEM, "lnl: no device memory for the factors of " + std::to_string(b_u) +
+                                    " bytes (K = " + std::to_string(plan.K) + ", G = " + std::to_string(plan.G) + ")");
   if ((rc = upload(c, s.u, plan.U.data(), b_u, "lnl factors"))) return rc;
-  if ((rc = upload(c, s.offs, offs, sizeof(int64_t) * ((size_t)n_psr + 1), "lnl offs"))) return rc;
-  if ((rc = upload(c, s.rows, plan.rows.data(), sizeof(int32_t) * (size_t)n_psr, "lnl rows"))) return rc;
   if ((rc = upload(c, s.ld, plan.ld.data(), sizeof(double) * plan.ld.size(), "lnl log-determinants"))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream), "lnl upload sync");
   return FPTA_OK;
 }
 
-// Both stages and the reduction on a block [R][ld]; one FPTA_K_DENSE entry. The results stay in the slot: X
-// [P][K][R_pad], q [P][G][R_pad], dlnL [G][R_pad].
-static int lnl_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K, int32_t G,
-                      const LnlSlot& s, int32_t& R_pad) {
-  R_pad = (R + kLnlRpad - 1) / kLnlRpad * kLnlRpad;
+// Both stages and the reduction on a block of st.K columns and st.G grid points; one FPTA_K_DENSE entry. The results
+// stay in the slot, padded to st.rpad realizations: X [P][K][rpad], q [P][G][rpad], dlnL [G][rpad].
+static int lnl_launch(fpta_ctx* c, const Block& b, LnlSlot& s, LnlState& st) {
+  const int32_t R = b.R, n_psr = b.n_psr, K = st.K, G = st.G;
+  const int32_t R_pad = st.rpad = (R + kLnlRpad - 1) / kLnlRpad * kLnlRpad;
   const size_t b_x = sizeof(double) * (size_t)n_psr * (size_t)K * (size_t)R_pad;
   const size_t b_q = sizeof(double) * (size_t)n_psr * (size_t)G * (size_t)R_pad, b_d = sizeof(double) * (size_t)G * R_pad;
-  if (s.coef.ensure(b_x) != hipSuccess || s.q.ensure(b_q) != hipSuccess || s.d.ensure(b_d) != hipSuccess)
+  if (s.x.coef.ensure(b_x) != hipSuccess || s.q.ensure(b_q) != hipSuccess || s.d.ensure(b_d) != hipSuccess)
     return fail(c, FPTA_ENOMEM, "lnl: no device memory for " + std::to_string(b_x + b_q + b_d) + " bytes of results");
   const int32_t KG = fpta_lnl::groups_of(K);
   const int nh = KG <= 8 ? 4 : 2;  // the X tile [16 KG][16 NH] doubles stays within 64 KB of LDS
@@ -183,12 +159,12 @@ static int lnl_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int
     return fail(c, FPTA_EINVAL, "lnl: too many realization tiles, grid chunks or pulsars");
   KTimer kt(c, FPTA_K_DENSE);
   int32_t rp = 0;
-  int rc = fit_launch_unbooked(c, res, ld, R, n_psr, K, s.a, s.offs, s.rows, s.coef, rp);
+  int rc = fit_launch_unbooked(c, b, K, s.x, rp);
   if (rc) return rc;
   if (rp != R_pad) return fail(c, FPTA_EINVAL, "lnl: k_fit_apply's realization padding changed");
   if (G == 0 || R == 0 || n_psr == 0) return FPTA_OK;
   LnlArgs a;
-  a.X = s.coef.as<double>();
+  a.X = s.x.coef.as<double>();
   a.U = s.u.as<double>();
   a.q = s.q.as<double>();
   a.u_stride = fpta_lnl::packed_size(K);
@@ -210,12 +186,13 @@ static int lnl_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int
   return FPTA_OK;
 }
 
-static int lnl_results(fpta_ctx* c, const LnlSlot& s, int32_t n_psr, int32_t K, int32_t G, int32_t R, int32_t R_pad,
-                       double* dlnl, double* q_psr, double* X) {
+// The wanted results of lnl_launch on that block, unpadded
+static int lnl_results(fpta_ctx* c, const Block& b, const LnlSlot& s, const LnlState& st, double* dlnl, double* q_psr,
+                       double* X) {
   int rc;
-  if (dlnl && (rc = fit_download(c, s.d, G, R, R_pad, dlnl))) return rc;
-  if (q_psr && (rc = fit_download(c, s.q, (int64_t)n_psr * G, R, R_pad, q_psr))) return rc;
-  if (X && (rc = fit_download(c, s.coef, (int64_t)n_psr * K, R, R_pad, X))) return rc;
+  if (dlnl && (rc = fit_download(c, s.d, st.G, b.R, st.rpad, dlnl))) return rc;
+  if (q_psr && (rc = fit_download(c, s.q, (int64_t)b.n_psr * st.G, b.R, st.rpad, q_psr))) return rc;
+  if (X && (rc = fit_download(c, s.x.coef, (int64_t)b.n_psr * st.K, b.R, st.rpad, X))) return rc;
   return FPTA_OK;
 }
 
@@ -232,30 +209,25 @@ extern "C" int fpta_batch_set_lnl(fpta_ctx* c, int32_t n_comp, const int32_t* n_
   const Layout& L = c->batch;
   if (L.P <= 0) return fail(c, FPTA_ESTATE, "set_lnl: set_toas first");
   if (n_comp == 0) {
-    c->has_lnl = false;
-    c->lnl_R = 0;
+    c->lnl_st.clear();
     if (rank_out) std::fill(rank_out, rank_out + L.P, 0);
     return FPTA_OK;
   }
   // everything is validated and the tables built here, before anything is uploaded
   std::string why;
   fpta_lnl::Plan plan;
-  const fpta_os::Spec sp = lnl_spec(n_comp, n_modes, f, f_is_common, idx, freqf, phi, mask, target);
+  const fpta_os::Spec sp =
+      fpta_os::make_spec(fpta_fit::make_spec(n_comp, n_modes, f, f_is_common, idx, freqf), phi, mask, target);
   const int made = fpta_lnl::make_plan(L.P, L.h_offs.data(), L.h_toas.data(), L.h_nu.data(), sp, n_col, M, ncol_psr,
                                        weights, rcond, n_grid, phi_grid, plan, why);
   if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, "set_lnl: " + why);
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  c->has_lnl = false;
-  c->lnl_R = 0;
+  c->lnl_st.clear();
   // a grid with the previous tables may still read them
   HIPCHK(c, hipStreamSynchronize(c->stream), "set_lnl sync");
-  const LnlSlot s{c->lnl_a, c->lnl_offs, c->lnl_rows, c->lnl_coef, c->lnl_u, c->lnl_ld, c->lnl_q, c->lnl_d};
   int rc;
-  if ((rc = lnl_upload(c, plan, L.P, L.h_offs.data(), s))) return rc;
-  c->has_lnl = true;
-  c->lnl_K = plan.K;
-  c->lnl_N = plan.N;
-  c->lnl_G = plan.G;
+  if ((rc = lnl_upload(c, plan, L.P, L.h_offs.data(), c->lnl))) return rc;
+  c->lnl_st = LnlState{true, plan.K, plan.N, plan.G};
   if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
   if (ld_out) std::copy(plan.ld.begin(), plan.ld.end(), ld_out);
   return FPTA_OK;
@@ -263,27 +235,23 @@ extern "C" int fpta_batch_set_lnl(fpta_ctx* c, int32_t n_comp, const int32_t* n_
 
 extern "C" int fpta_batch_lnl_info(fpta_ctx* c, int64_t* info) {
   if (!c || !info) return fail(c, FPTA_EINVAL, "lnl_info: bad arguments");
-  info[0] = c->has_lnl ? c->lnl_K : 0;
-  info[1] = c->has_lnl ? c->lnl_N : 0;
-  info[2] = c->has_lnl ? c->lnl_G : 0;
-  info[3] = c->has_lnl ? c->lnl_R : 0;
+  const LnlState& st = c->lnl_st;  // all zero while no grid is set
+  const int64_t v[4] = {st.K, st.N, st.G, st.R};
+  std::copy(v, v + 4, info);
   return FPTA_OK;
 }
 
 extern "C" int fpta_batch_lnl(fpta_ctx* c, double* dlnl, double* q_psr, double* X) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (!c->out_R) return fail(c, FPTA_ESTATE, "lnl: nothing synthesized yet");
-  if (!c->has_lnl) return fail(c, FPTA_ESTATE, "lnl: no likelihood grid is set (set_lnl first)");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc = join_red(c);  // a streamed job's reductions may still run beside the ctx stream
-  if (rc) return rc;
-  c->lnl_R = 0;
-  const LnlSlot s{c->lnl_a, c->lnl_offs, c->lnl_rows, c->lnl_coef, c->lnl_u, c->lnl_ld, c->lnl_q, c->lnl_d};
-  // the block is read only: part_ready and the next-block mix stay as they are
-  if ((rc = lnl_launch(c, c->out.as<double>(), c->out_ld, c->out_R, c->batch.P, c->lnl_K, c->lnl_G, s, c->lnl_rpad)))
-    return rc;
-  c->lnl_R = c->out_R;
-  return lnl_results(c, s, c->batch.P, c->lnl_K, c->lnl_G, c->lnl_R, c->lnl_rpad, dlnl, q_psr, X);
+  Block b;
+  int rc;
+  if ((rc = block_check(c, "lnl", false, b))) return rc;
+  LnlState& st = c->lnl_st;
+  if (!st.set) return fail(c, FPTA_ESTATE, "lnl: no likelihood grid is set (set_lnl first)");
+  if ((rc = block_open(c, false))) return rc;
+  st.R = 0;
+  if ((rc = lnl_launch(c, b, c->lnl, st))) return rc;
+  st.R = b.R;
+  return lnl_results(c, b, c->lnl, st, dlnl, q_psr, X);
 }
 
 extern "C" int fpta_lnl_grid(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const double* toas, const double* nu,
@@ -293,34 +261,30 @@ extern "C" int fpta_lnl_grid(fpta_ctx* c, int32_t n_psr, const int64_t* offs, co
                              const double* weights, double rcond, int32_t n_grid, const double* phi_grid,
                              int32_t n_vec, const double* res, double* dlnl, double* q_psr, double* X,
                              int32_t* rank_out, double* ld_out, double* U_out) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (n_psr < 0 || n_vec < 0 || (n_psr > 0 && !offs)) return fail(c, FPTA_EINVAL, "lnl_grid: bad arguments");
+  const OneShot one{c, "lnl_grid", n_psr, offs, n_vec, res};
+  int rc;
+  if ((rc = one.check())) return rc;
   std::string why;
   fpta_lnl::Plan plan;
-  const fpta_os::Spec sp = lnl_spec(n_comp, n_modes, f, f_is_common, idx, freqf, phi, mask, target);
+  const fpta_os::Spec sp =
+      fpta_os::make_spec(fpta_fit::make_spec(n_comp, n_modes, f, f_is_common, idx, freqf), phi, mask, target);
   const int made = fpta_lnl::make_plan(n_psr, offs, toas, nu, sp, n_col, M, ncol_psr, weights, rcond, n_grid, phi_grid,
                                        plan, why, U_out);
-  if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, "lnl_grid: " + why);
-  const int64_t n_toa = n_psr > 0 ? offs[n_psr] : 0;
-  if (n_vec > 0 && n_toa > 0 && !res) return fail(c, FPTA_EINVAL, "lnl_grid: res missing");
+  if ((rc = one.planned(made, why))) return rc;
   if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
   if (ld_out) std::copy(plan.ld.begin(), plan.ld.end(), ld_out);
   if (n_vec == 0) return FPTA_OK;
-  if (n_psr == 0 || n_toa == 0) {  // nothing to launch: every X and q is zero and so is every log-determinant
+  if (n_psr == 0 || one.n_toa() == 0) {  // nothing to launch: every X and q is zero and so is every log-determinant
     if (dlnl) std::fill(dlnl, dlnl + (int64_t)plan.G * n_vec, 0.0);
     if (q_psr) std::fill(q_psr, q_psr + (int64_t)n_psr * plan.G * n_vec, 0.0);
     if (X) std::fill(X, X + (int64_t)n_psr * plan.K * n_vec, 0.0);
     return FPTA_OK;
   }
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  const LnlSlot s{c->lnl1_a, c->lnl1_offs, c->lnl1_rows, c->lnl1_coef, c->lnl1_u, c->lnl1_ld, c->lnl1_q, c->lnl1_d};
-  int rc;
-  if ((rc = lnl_upload(c, plan, n_psr, offs, s))) return rc;
-  if ((rc = upload(c, c->lnl1_res, res, sizeof(double) * (size_t)n_vec * (size_t)n_toa, "lnl_grid residuals")))
-    return rc;
-  int32_t R_pad = 0;
-  if ((rc = lnl_launch(c, c->lnl1_res.as<double>(), n_toa, n_vec, n_psr, plan.K, plan.G, s, R_pad))) return rc;
-  if ((rc = lnl_results(c, s, n_psr, plan.K, plan.G, n_vec, R_pad, dlnl, q_psr, X))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream), "lnl_grid sync");  // the residuals' upload is done with its source
-  return FPTA_OK;
+  Block b;
+  if ((rc = one.upload(b))) return rc;
+  if ((rc = lnl_upload(c, plan, n_psr, offs, c->lnl1))) return rc;
+  LnlState st{true, plan.K, plan.N, plan.G};
+  if ((rc = lnl_launch(c, b, c->lnl1, st))) return rc;
+  if ((rc = lnl_results(c, b, c->lnl1, st, dlnl, q_psr, X))) return rc;
+  return one.done();
 }

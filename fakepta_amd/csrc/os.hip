@@ -141,39 +141,11 @@ __global__ __launch_bounds__(256) void k_os_reduce(const double* __restrict__ Qm
   Q[e] = s;
 }
 
-// One slot: the device tables of a statistic and its results
-struct OsSlot {
-  DevBuf &a, &offs, &rows, &coef, &phi, &g, &qm, &q;
-};
-
-static fpta_os::Spec os_spec(int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
-                             const double* idx, const double* freqf, const double* phi, const uint8_t* mask,
-                             int32_t target, const double* phi_hat) {
-  fpta_os::Spec sp;
-  sp.comps.n_comp = n_comp;
-  sp.comps.n_modes = n_modes;
-  sp.comps.f = f;
-  sp.comps.f_is_common = f_is_common != 0;
-  sp.comps.idx = idx;
-  sp.comps.freqf = freqf;
-  sp.phi = phi;
-  sp.mask = mask;
-  sp.target = target;
-  sp.phi_hat = phi_hat;
-  return sp;
-}
-
-// Device copies of a plan's tables, the template and the matrices. The operator is the large one (8 K n_toa bytes).
+// Device copies of a plan's tables, the template and the matrices
 static int os_upload(fpta_ctx* c, const fpta_os::Plan& plan, int32_t n_psr, const int64_t* offs, const double* phi_hat,
-                     int32_t n_g, const double* G, const OsSlot& s) {
-  const size_t bytes = sizeof(double) * plan.B.size();
-  if (s.a.ensure(bytes) != hipSuccess)
-    return fail(c, FPTA_ENOMEM, "os: no device memory for the operator of " + std::to_string(bytes) +
-                                    " bytes (8 K n_toa, K = " + std::to_string(plan.K) + ")");
+                     int32_t n_g, const double* G, OsSlot& s) {
   int rc;
-  if ((rc = upload(c, s.a, plan.B.data(), bytes, "os operator"))) return rc;
-  if ((rc = upload(c, s.offs, offs, sizeof(int64_t) * ((size_t)n_psr + 1), "os offs"))) return rc;
-  if ((rc = upload(c, s.rows, plan.rows.data(), sizeof(int32_t) * (size_t)n_psr, "os rows"))) return rc;
+  if ((rc = fit_upload(c, "os", s.x, plan.K, plan.B, n_psr, offs, plan.rows))) return rc;
   if ((rc = upload(c, s.phi, phi_hat, sizeof(double) * (size_t)plan.N, "os template"))) return rc;
   if ((rc = upload(c, s.g, G, sizeof(double) * (size_t)n_g * (size_t)n_psr * (size_t)n_psr, "os pair weights")))
     return rc;
@@ -181,27 +153,26 @@ static int os_upload(fpta_ctx* c, const fpta_os::Plan& plan, int32_t n_psr, cons
   return FPTA_OK;
 }
 
-// Both stages on a block [R][ld]; one FPTA_K_DENSE entry. The results stay in the slot: X [P][K][R_pad], Q_mode
-// [J][N][R_pad], Q [J][R_pad].
-static int os_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int32_t n_psr, int32_t K, int32_t J,
-                     const OsSlot& s, int32_t& R_pad) {
-  R_pad = (R + kOsRpad - 1) / kOsRpad * kOsRpad;
-  const int32_t N = K / 2;
+// Both stages on a block of st.K columns and st.J matrices; one FPTA_K_DENSE entry. The results stay in the slot, padded
+// to st.rpad realizations: X [P][K][rpad], Q_mode [J][N][rpad], Q [J][rpad].
+static int os_launch(fpta_ctx* c, const Block& b, OsSlot& s, OsState& st) {
+  const int32_t R = b.R, n_psr = b.n_psr, K = st.K, J = st.J, N = K / 2;
+  const int32_t R_pad = st.rpad = (R + kOsRpad - 1) / kOsRpad * kOsRpad;
   const size_t b_x = sizeof(double) * (size_t)n_psr * (size_t)K * (size_t)R_pad;
   const size_t b_qm = sizeof(double) * (size_t)J * (size_t)N * (size_t)R_pad, b_q = sizeof(double) * (size_t)J * R_pad;
-  if (s.coef.ensure(b_x) != hipSuccess || s.qm.ensure(b_qm) != hipSuccess || s.q.ensure(b_q) != hipSuccess)
+  if (s.x.coef.ensure(b_x) != hipSuccess || s.qm.ensure(b_qm) != hipSuccess || s.q.ensure(b_q) != hipSuccess)
     return fail(c, FPTA_ENOMEM, "os: no device memory for " + std::to_string(b_x + b_qm + b_q) + " bytes of results");
   const int jc = J <= 1 ? 1 : J <= 2 ? 2 : J <= 4 ? 4 : kOsJ;  // matrices per workgroup
   const int64_t n_jc = (J + jc - 1) / jc;
   if (n_jc > 65535 || N > 65535) return fail(c, FPTA_EINVAL, "os: too many pair-weight matrices or modes");
   KTimer kt(c, FPTA_K_DENSE);
   int32_t rp = 0;
-  int rc = fit_launch_unbooked(c, res, ld, R, n_psr, K, s.a, s.offs, s.rows, s.coef, rp);
+  int rc = fit_launch_unbooked(c, b, K, s.x, rp);
   if (rc) return rc;
   if (rp != R_pad) return fail(c, FPTA_EINVAL, "os: k_fit_apply's realization padding changed");
   if (J == 0 || R == 0) return FPTA_OK;
   OsArgs a;
-  a.X = s.coef.as<double>();
+  a.X = s.x.coef.as<double>();
   a.phi = s.phi.as<double>();
   a.G = s.g.as<double>();
   a.Qm = s.qm.as<double>();
@@ -227,12 +198,13 @@ static int os_launch(fpta_ctx* c, const double* res, int64_t ld, int32_t R, int3
   return FPTA_OK;
 }
 
-static int os_results(fpta_ctx* c, const OsSlot& s, int32_t n_psr, int32_t K, int32_t J, int32_t R, int32_t R_pad,
-                      double* Q, double* Q_mode, double* X) {
+// The wanted results of os_launch on that block, unpadded
+static int os_results(fpta_ctx* c, const Block& b, const OsSlot& s, const OsState& st, double* Q, double* Q_mode,
+                      double* X) {
   int rc;
-  if (Q && J > 0 && (rc = fit_download(c, s.q, J, R, R_pad, Q))) return rc;
-  if (Q_mode && J > 0 && (rc = fit_download(c, s.qm, (int64_t)J * (K / 2), R, R_pad, Q_mode))) return rc;
-  if (X && (rc = fit_download(c, s.coef, (int64_t)n_psr * K, R, R_pad, X))) return rc;
+  if (Q && st.J > 0 && (rc = fit_download(c, s.q, st.J, b.R, st.rpad, Q))) return rc;
+  if (Q_mode && st.J > 0 && (rc = fit_download(c, s.qm, (int64_t)st.J * st.N, b.R, st.rpad, Q_mode))) return rc;
+  if (X && (rc = fit_download(c, s.x.coef, (int64_t)b.n_psr * st.K, b.R, st.rpad, X))) return rc;
   return FPTA_OK;
 }
 
@@ -249,30 +221,25 @@ extern "C" int fpta_batch_set_os(fpta_ctx* c, int32_t n_comp, const int32_t* n_m
   const Layout& L = c->batch;
   if (L.P <= 0) return fail(c, FPTA_ESTATE, "set_os: set_toas first");
   if (n_comp == 0) {
-    c->has_os = false;
-    c->os_R = 0;
+    c->os_st.clear();
     if (rank_out) std::fill(rank_out, rank_out + L.P, 0);
     return FPTA_OK;
   }
   // everything is validated and the operators built here, before anything is uploaded
   std::string why;
   fpta_os::Plan plan;
-  const fpta_os::Spec sp = os_spec(n_comp, n_modes, f, f_is_common, idx, freqf, phi, mask, target, phi_hat);
+  const fpta_os::Spec sp = fpta_os::make_spec(fpta_fit::make_spec(n_comp, n_modes, f, f_is_common, idx, freqf), phi,
+                                              mask, target, phi_hat);
   const int made = fpta_os::make_plan(L.P, L.h_offs.data(), L.h_toas.data(), L.h_nu.data(), sp, n_col, M, ncol_psr,
                                       weights, rcond, n_g, G, plan, why);
   if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, "set_os: " + why);
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  c->has_os = false;
-  c->os_R = 0;
+  c->os_st.clear();
   // a statistic with the previous operator may still read the tables
   HIPCHK(c, hipStreamSynchronize(c->stream), "set_os sync");
-  const OsSlot s{c->os_a, c->os_offs, c->os_rows, c->os_coef, c->os_phi, c->os_g, c->os_qm, c->os_q};
   int rc;
-  if ((rc = os_upload(c, plan, L.P, L.h_offs.data(), phi_hat, n_g, G, s))) return rc;
-  c->has_os = true;
-  c->os_K = plan.K;
-  c->os_N = plan.N;
-  c->os_J = n_g;
+  if ((rc = os_upload(c, plan, L.P, L.h_offs.data(), phi_hat, n_g, G, c->os))) return rc;
+  c->os_st = OsState{true, plan.K, plan.N, n_g};
   if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
   if (nab_out) std::copy(plan.Nab.begin(), plan.Nab.end(), nab_out);
   return FPTA_OK;
@@ -280,27 +247,23 @@ extern "C" int fpta_batch_set_os(fpta_ctx* c, int32_t n_comp, const int32_t* n_m
 
 extern "C" int fpta_batch_os_info(fpta_ctx* c, int64_t* info) {
   if (!c || !info) return fail(c, FPTA_EINVAL, "os_info: bad arguments");
-  info[0] = c->has_os ? c->os_K : 0;
-  info[1] = c->has_os ? c->os_N : 0;
-  info[2] = c->has_os ? c->os_J : 0;
-  info[3] = c->has_os ? c->os_R : 0;
+  const OsState& st = c->os_st;  // all zero while no statistic is set
+  const int64_t v[4] = {st.K, st.N, st.J, st.R};
+  std::copy(v, v + 4, info);
   return FPTA_OK;
 }
 
 extern "C" int fpta_batch_os(fpta_ctx* c, double* Q, double* Q_mode, double* X) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (!c->out_R) return fail(c, FPTA_ESTATE, "os: nothing synthesized yet");
-  if (!c->has_os) return fail(c, FPTA_ESTATE, "os: no optimal statistic is set (set_os first)");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc = join_red(c);  // a streamed job's reductions may still run beside the ctx stream
-  if (rc) return rc;
-  c->os_R = 0;
-  const OsSlot s{c->os_a, c->os_offs, c->os_rows, c->os_coef, c->os_phi, c->os_g, c->os_qm, c->os_q};
-  // the block is read only: part_ready and the next-block mix stay as they are
-  if ((rc = os_launch(c, c->out.as<double>(), c->out_ld, c->out_R, c->batch.P, c->os_K, c->os_J, s, c->os_rpad)))
-    return rc;
-  c->os_R = c->out_R;
-  return os_results(c, s, c->batch.P, c->os_K, c->os_J, c->os_R, c->os_rpad, Q, Q_mode, X);
+  Block b;
+  int rc;
+  if ((rc = block_check(c, "os", false, b))) return rc;
+  OsState& st = c->os_st;
+  if (!st.set) return fail(c, FPTA_ESTATE, "os: no optimal statistic is set (set_os first)");
+  if ((rc = block_open(c, false))) return rc;
+  st.R = 0;
+  if ((rc = os_launch(c, b, c->os, st))) return rc;
+  st.R = b.R;
+  return os_results(c, b, c->os, st, Q, Q_mode, X);
 }
 
 extern "C" int fpta_os_statistic(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const double* toas, const double* nu,
@@ -310,33 +273,29 @@ extern "C" int fpta_os_statistic(fpta_ctx* c, int32_t n_psr, const int64_t* offs
                                  const int32_t* ncol_psr, const double* weights, double rcond, int32_t n_g,
                                  const double* G, int32_t n_vec, const double* res, double* Q, double* Q_mode,
                                  double* X, int32_t* rank_out, double* nab_out) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (n_psr < 0 || n_vec < 0 || (n_psr > 0 && !offs)) return fail(c, FPTA_EINVAL, "os_statistic: bad arguments");
+  const OneShot one{c, "os_statistic", n_psr, offs, n_vec, res};
+  int rc;
+  if ((rc = one.check())) return rc;
   std::string why;
   fpta_os::Plan plan;
-  const fpta_os::Spec sp = os_spec(n_comp, n_modes, f, f_is_common, idx, freqf, phi, mask, target, phi_hat);
+  const fpta_os::Spec sp = fpta_os::make_spec(fpta_fit::make_spec(n_comp, n_modes, f, f_is_common, idx, freqf), phi,
+                                              mask, target, phi_hat);
   const int made = fpta_os::make_plan(n_psr, offs, toas, nu, sp, n_col, M, ncol_psr, weights, rcond, n_g, G, plan, why);
-  if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, "os_statistic: " + why);
-  const int64_t n_toa = n_psr > 0 ? offs[n_psr] : 0;
-  if (n_vec > 0 && n_toa > 0 && !res) return fail(c, FPTA_EINVAL, "os_statistic: res missing");
+  if ((rc = one.planned(made, why))) return rc;
   if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
   if (nab_out) std::copy(plan.Nab.begin(), plan.Nab.end(), nab_out);
   if (n_vec == 0) return FPTA_OK;
-  if (n_psr == 0 || n_toa == 0) {  // nothing to launch: every X and every Q is zero
+  if (n_psr == 0 || one.n_toa() == 0) {  // nothing to launch: every X and every Q is zero
     if (Q) std::fill(Q, Q + (int64_t)n_g * n_vec, 0.0);
     if (Q_mode) std::fill(Q_mode, Q_mode + (int64_t)n_g * plan.N * n_vec, 0.0);
     if (X) std::fill(X, X + (int64_t)n_psr * plan.K * n_vec, 0.0);
     return FPTA_OK;
   }
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  const OsSlot s{c->os1_a, c->os1_offs, c->os1_rows, c->os1_coef, c->os1_phi, c->os1_g, c->os1_qm, c->os1_q};
-  int rc;
-  if ((rc = os_upload(c, plan, n_psr, offs, phi_hat, n_g, G, s))) return rc;
-  if ((rc = upload(c, c->os1_res, res, sizeof(double) * (size_t)n_vec * (size_t)n_toa, "os_statistic residuals")))
-    return rc;
-  int32_t R_pad = 0;
-  if ((rc = os_launch(c, c->os1_res.as<double>(), n_toa, n_vec, n_psr, plan.K, n_g, s, R_pad))) return rc;
-  if ((rc = os_results(c, s, n_psr, plan.K, n_g, n_vec, R_pad, Q, Q_mode, X))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream), "os_statistic sync");  // the residuals' upload is done with its source
-  return FPTA_OK;
+  Block b;
+  if ((rc = one.upload(b))) return rc;
+  if ((rc = os_upload(c, plan, n_psr, offs, phi_hat, n_g, G, c->os1))) return rc;
+  OsState st{true, plan.K, plan.N, n_g};
+  if ((rc = os_launch(c, b, c->os1, st))) return rc;
+  if ((rc = os_results(c, b, c->os1, st, Q, Q_mode, X))) return rc;
+  return one.done();
 }

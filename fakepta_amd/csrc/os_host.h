@@ -36,6 +36,18 @@ struct Spec {
   const double* phi_hat = nullptr;
 };
 
+// The same from the C entry points' arguments (the likelihood grid has no template)
+inline Spec make_spec(const fpta_fit::Spec& comps, const double* phi, const uint8_t* mask, int32_t target,
+                      const double* phi_hat = nullptr) {
+  Spec sp;
+  sp.comps = comps;
+  sp.phi = phi;
+  sp.mask = mask;
+  sp.target = target;
+  sp.phi_hat = phi_hat;
+  return sp;
+}
+
 // Everything the entry points refuse beyond fit_host.h's validate. G: n_g pair-weight matrices [n_psr][n_psr].
 inline bool validate(int64_t n_psr, const int64_t* offs, const double* toas, const double* nu, const Spec& sp,
                      int64_t n_col, const double* M, const int32_t* ncol_psr, const double* weights, int32_t n_g,

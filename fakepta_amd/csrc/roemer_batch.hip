@@ -18,9 +18,9 @@
 //                   nothing, a chunk without rows leaves before the prologue; spare lanes of a partial slab repeat its
 //                   last TOA and store nothing. No atomics, the block is read and written once.
 //   one table for every realization: the delay vector is made once by k_roemer_main<false> on zeros (the drop-in
-//                   call's own arithmetic) and added to every row by k_cw_bcast (cw_batch.hip).
+//                   call's own arithmetic) and added to every row by k_cw_bcast (cw_batch.hip), through the helpers
+//                   of the one-table mode that both injections share (bcast_vector, bcast_add).
 #include "capi_host.h"
-#include "cw_device.h"
 #include "ephem_device.h"
 #include "roemer_batch_host.h"
 #include "device_common.h"
@@ -102,13 +102,13 @@ using namespace capi;
 
 extern "C" int fpta_batch_roemer_accumulate(fpta_ctx* c, const double* pos, int32_t n_tab, const int64_t* row_offs,
                                             const double* rows, double sign) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
+  const char* who = "batch_roemer_accumulate";
+  Block b;
+  int rc;
+  if ((rc = block_check(c, who, true, b))) return rc;
   const Layout& L = c->batch;
-  if (L.P <= 0) return fail(c, FPTA_ESTATE, "batch_roemer_accumulate: set_toas first");
-  if (!c->out_R) return fail(c, FPTA_ESTATE, "batch_roemer_accumulate: nothing synthesized yet");
-  const int32_t R = c->out_R;
-  const int64_t ld = c->out_ld, n_toa = L.n_toa;
-  if (n_toa > ld) return fail(c, FPTA_ESTATE, "batch_roemer_accumulate: the block is narrower than the layout");
+  const int32_t R = b.R;
+  const int64_t n_toa = L.n_toa;
   // everything is validated and the row records made here, before anything is uploaded or launched
   fpta_roemerb::Plan plan;
   std::string why;
@@ -118,27 +118,17 @@ extern "C" int fpta_batch_roemer_accumulate(fpta_ctx* c, const double* pos, int3
   if (plan.n_row == 0 || n_toa == 0) return FPTA_OK;  // the block, and what is known about it, stay as they are
   const bool shared = n_tab == 1;  // every realization gets the same delay vector
   const int64_t n_slab = (int64_t)plan.slabs.size(), n_cg = ((int64_t)R + plan.chunk - 1) / plan.chunk;
-  const int64_t n_chunk = (n_toa + 255) / 256, n_rg = ((int64_t)R + kCwbRows - 1) / kCwbRows;
-  if (shared ? n_chunk * n_rg > 0x7FFFFFFF : n_slab * n_cg > 0x7FFFFFFF)
-    return fail(c, FPTA_EINVAL, "batch_roemer_accumulate: block too large");
+  if (!shared && n_slab * n_cg > 0x7FFFFFFF) return fail(c, FPTA_EINVAL, "batch_roemer_accumulate: block too large");
 
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc = join_red(c);  // a streamed job's reductions may still run beside the ctx stream
-  if (rc) return rc;
-  c->part_ready = false;  // the interpolation's partial checksums describe the block before the injection
-  double* block = c->out.as<double>();
+  if ((rc = block_open(c, true))) return rc;
   std::vector<EphWave> waves;  // (lives until the sync below)
   if (shared) {
-    HIPCHK(c, c->rmb_v.ensure(sizeof(double) * (size_t)n_toa), "roemer batch delay vector");
-    HIPCHK(c, hipMemsetAsync(c->rmb_v.p, 0, sizeof(double) * (size_t)n_toa, c->stream),
-           "roemer batch delay vector clear");
+    if ((rc = bcast_vector(c, who, c->rmb_v))) return rc;
     KTimer kt(c, FPTA_K_EPHEM);
     if ((rc = roemer_sum_launch(c, L.P, L.h_offs.data(), L.toas.as<double>(), pos, plan.rows, sign, n_toa, waves,
                                 c->rmb_v.as<double>())))
       return rc;
-    k_cw_bcast<<<dim3((unsigned)(n_chunk * n_rg)), dim3(256), 0, c->stream>>>(c->rmb_v.as<double>(), n_toa,
-                                                                             (uint32_t)n_chunk, R, ld, block);
-    HIPCHK(c, hipGetLastError(), "k_cw_bcast launch");
+    if ((rc = bcast_add(c, who, c->rmb_v, b))) return rc;
   } else {
     const fpta_ephem::Obliquity ob = fpta_ephem::obliquity();
     const int32_t n_base = (int32_t)plan.bases.size();
@@ -159,7 +149,7 @@ extern "C" int fpta_batch_roemer_accumulate(fpta_ctx* c, const double* pos, int3
     k_roemer_block<<<dim3((unsigned)(n_slab * n_cg)), dim3(kRmbThreads), lds, c->stream>>>(
         c->rmb_slabs.as<Slab>(), (uint32_t)n_slab, L.toas.as<double>(), n_toa, c->rmb_pos.as<double>(),
         c->rmb_offs.as<int64_t>(), c->rmb_rows.as<RoemerRow>(), c->rmb_slots.as<int32_t>(), c->rmb_bases.as<Body>(),
-        n_base, ob.sn, ob.cs, sign, R, plan.chunk, ld, block);
+        n_base, ob.sn, ob.cs, sign, R, plan.chunk, b.ld, b.res);
     HIPCHK(c, hipGetLastError(), "k_roemer_block launch");
   }
   // the tables above are this call's own host memory: the stream has taken them once it has run

@@ -142,18 +142,17 @@ __global__ __launch_bounds__(64 * kTmWaves) void k_tm_project(TmArgs a) {
 }
 
 // The launch of a block [R][ld] against device tables; n_psr x ceil(R / 16) workgroups
-static int tm_launch(fpta_ctx* c, double* res, int64_t ld, int32_t R, int32_t n_psr, const DevBuf& Q, const DevBuf& s,
-                     const DevBuf& offs, const DevBuf& rank) {
+static int tm_launch(fpta_ctx* c, const Block& b, const TmSlot& s) {
   TmArgs a;
-  a.res = res;
-  a.ld = ld;
-  a.R = R;
-  a.n_rt = (R + kTmReal - 1) / kTmReal;
-  a.Q = Q.as<double>();
-  a.s = s.as<double>();
-  a.offs = offs.as<int64_t>();
-  a.rank = rank.as<int32_t>();
-  const int64_t blocks = (int64_t)n_psr * a.n_rt;
+  a.res = b.res;
+  a.ld = b.ld;
+  a.R = b.R;
+  a.n_rt = (b.R + kTmReal - 1) / kTmReal;
+  a.Q = s.q.as<double>();
+  a.s = s.s.as<double>();
+  a.offs = s.offs.as<int64_t>();
+  a.rank = s.rank.as<int32_t>();
+  const int64_t blocks = (int64_t)b.n_psr * a.n_rt;
   if (blocks > 0x7FFFFFFF) return fail(c, FPTA_EINVAL, "tm_project: too many pulsars x realization tiles");
   KTimer kt(c, FPTA_K_DENSE);
   k_tm_project<<<dim3((unsigned)blocks), dim3(64 * kTmWaves), 0, c->stream>>>(a);
@@ -161,13 +160,12 @@ static int tm_launch(fpta_ctx* c, double* res, int64_t ld, int32_t R, int32_t n_
   return FPTA_OK;
 }
 
-static int tm_upload(fpta_ctx* c, const fpta_tm::Plan& plan, int32_t n_psr, const int64_t* offs, DevBuf& Q, DevBuf& s,
-                     DevBuf& d_offs, DevBuf& rank) {
+static int tm_upload(fpta_ctx* c, const fpta_tm::Plan& plan, int32_t n_psr, const int64_t* offs, TmSlot& s) {
   int rc;
-  if ((rc = upload(c, Q, plan.Q.data(), sizeof(double) * plan.Q.size(), "tm basis"))) return rc;
-  if ((rc = upload(c, s, plan.s.data(), sizeof(double) * plan.s.size(), "tm weights"))) return rc;
-  if ((rc = upload(c, d_offs, offs, sizeof(int64_t) * ((size_t)n_psr + 1), "tm offs"))) return rc;
-  if ((rc = upload(c, rank, plan.rank.data(), sizeof(int32_t) * (size_t)n_psr, "tm ranks"))) return rc;
+  if ((rc = upload(c, s.q, plan.Q.data(), sizeof(double) * plan.Q.size(), "tm basis"))) return rc;
+  if ((rc = upload(c, s.s, plan.s.data(), sizeof(double) * plan.s.size(), "tm weights"))) return rc;
+  if ((rc = upload(c, s.offs, offs, sizeof(int64_t) * ((size_t)n_psr + 1), "tm offs"))) return rc;
+  if ((rc = upload(c, s.rank, plan.rank.data(), sizeof(int32_t) * (size_t)n_psr, "tm ranks"))) return rc;
   return FPTA_OK;
 }
 
@@ -181,7 +179,7 @@ extern "C" int fpta_batch_set_timing_model(fpta_ctx* c, int32_t n_col, const dou
   const Layout& L = c->batch;
   if (L.P <= 0) return fail(c, FPTA_ESTATE, "set_timing_model: set_toas first");
   if (n_col == 0) {
-    c->has_tm = false;
+    c->tm_st.clear();
     if (rank_out) std::fill(rank_out, rank_out + L.P, 0);
     return FPTA_OK;
   }
@@ -191,49 +189,43 @@ extern "C" int fpta_batch_set_timing_model(fpta_ctx* c, int32_t n_col, const dou
   if (!fpta_tm::make_plan(L.P, L.h_offs.data(), n_col, M, ncol_psr, weights, rcond, plan, why))
     return fail(c, FPTA_EINVAL, "set_timing_model: " + why);
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  c->has_tm = false;
+  c->tm_st.clear();
   // a projection of the previous model may still read the tables (an upload into a buffer that does not grow)
   HIPCHK(c, hipStreamSynchronize(c->stream), "set_timing_model sync");
   int rc;
-  if ((rc = tm_upload(c, plan, L.P, L.h_offs.data(), c->tm_q, c->tm_s, c->tm_offs, c->tm_rank))) return rc;
+  if ((rc = tm_upload(c, plan, L.P, L.h_offs.data(), c->tm))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream), "set_timing_model sync");
-  c->has_tm = true;
+  c->tm_st.set = true;
   if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
   return FPTA_OK;
 }
 
 extern "C" int fpta_batch_project(fpta_ctx* c) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (!c->out_R) return fail(c, FPTA_ESTATE, "project: nothing synthesized yet");
-  if (!c->has_tm) return fail(c, FPTA_ESTATE, "project: no timing model (set_timing_model first)");
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc = join_red(c);  // a streamed job's reductions may still run beside the ctx stream
-  if (rc) return rc;
-  c->part_ready = false;  // the interpolation's partial checksums describe the block before the projection
-  return tm_launch(c, c->out.as<double>(), c->out_ld, c->out_R, c->batch.P, c->tm_q, c->tm_s, c->tm_offs, c->tm_rank);
+  Block b;
+  int rc;
+  if ((rc = block_check(c, "project", false, b))) return rc;
+  if (!c->tm_st.set) return fail(c, FPTA_ESTATE, "project: no timing model (set_timing_model first)");
+  if ((rc = block_open(c, true))) return rc;
+  return tm_launch(c, b, c->tm);
 }
 
 extern "C" int fpta_tm_project(fpta_ctx* c, int32_t n_psr, const int64_t* offs, const double* M, int32_t n_col,
                                const int32_t* ncol_psr, const double* weights, double rcond, int32_t n_vec, double* res,
                                int32_t* rank_out) {
-  if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (n_psr < 0 || n_vec < 0 || (n_psr > 0 && !offs)) return fail(c, FPTA_EINVAL, "tm_project: bad arguments");
+  const OneShot one{c, "tm_project", n_psr, offs, n_vec, res};
+  int rc;
+  if ((rc = one.check())) return rc;
   std::string why;
   fpta_tm::Plan plan;
-  if (!fpta_tm::make_plan(n_psr, offs, n_col, M, ncol_psr, weights, rcond, plan, why))
-    return fail(c, FPTA_EINVAL, "tm_project: " + why);
-  const int64_t n_toa = n_psr > 0 ? offs[n_psr] : 0;
-  if (n_vec > 0 && n_toa > 0 && !res) return fail(c, FPTA_EINVAL, "tm_project: res missing");
+  const bool made = fpta_tm::make_plan(n_psr, offs, n_col, M, ncol_psr, weights, rcond, plan, why);
+  if ((rc = one.planned(made ? 0 : 1, why))) return rc;
   if (rank_out) std::copy(plan.rank.begin(), plan.rank.end(), rank_out);
-  if (n_psr == 0 || n_vec == 0 || n_toa == 0 || plan.max_rank == 0) return FPTA_OK;  // res stays as it is
-  HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
-  int rc;
-  if ((rc = tm_upload(c, plan, n_psr, offs, c->tm1_q, c->tm1_s, c->tm1_offs, c->tm1_rank))) return rc;
-  const size_t bytes = sizeof(double) * (size_t)n_vec * (size_t)n_toa;
-  if ((rc = upload(c, c->tm1_res, res, bytes, "tm_project residuals"))) return rc;
-  if ((rc = tm_launch(c, c->tm1_res.as<double>(), n_toa, n_vec, n_psr, c->tm1_q, c->tm1_s, c->tm1_offs, c->tm1_rank)))
-    return rc;
-  HIPCHK(c, hipMemcpyAsync(res, c->tm1_res.p, bytes, hipMemcpyDeviceToHost, c->stream), "tm_project download");
-  HIPCHK(c, hipStreamSynchronize(c->stream), "tm_project sync");
-  return FPTA_OK;
+  if (n_psr == 0 || n_vec == 0 || one.n_toa() == 0 || plan.max_rank == 0) return FPTA_OK;  // res stays as it is
+  Block b;
+  if ((rc = one.upload(b))) return rc;
+  if ((rc = tm_upload(c, plan, n_psr, offs, c->tm1))) return rc;
+  if ((rc = tm_launch(c, b, c->tm1))) return rc;
+  HIPCHK(c, hipMemcpyAsync(res, b.res, sizeof(double) * (size_t)b.R * (size_t)b.ld, hipMemcpyDeviceToHost, c->stream),
+         "tm_project download");
+  return one.done();
 }

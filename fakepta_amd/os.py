@@ -223,22 +223,7 @@ def segments_of(psrs, names=None):
     return out
 
 
-def design_of(psrs, Mmats, what):
-    """Mmats "tm" (each pulsar's Mmat), None (nothing marginalised) or a list of [n_p, m_p <= 16] -> (M, ncol_psr)."""
-    if isinstance(Mmats, str):
-        if Mmats != "tm":
-            raise ValueError(f"{what}: Mmats must be 'tm', None or a list of matrices, got {Mmats!r}")
-        Mmats = [p.Mmat for p in psrs]
-    if Mmats is None:
-        Mmats = [np.zeros((len(p.toas), 0)) for p in psrs]
-    Mmats = list(Mmats)
-    if len(Mmats) != len(psrs):
-        raise ValueError(f"{what}: {len(Mmats)} design matrices for {len(psrs)} pulsars")
-    for i, (m, p) in enumerate(zip(Mmats, psrs)):
-        if np.ndim(m) != 2 or np.shape(m)[0] != len(p.toas):
-            raise ValueError(f"{what}: design matrix of pulsar {i} must be [{len(p.toas)}, n_col], got shape "
-                             f"{np.shape(m)}")
-    return _tm.stack_design(Mmats)
+design_of = _tm.design_of  # (lnl.py takes it from here)
 
 
 def statistic_array(psrs, target=None, orfs=("hd",), bins=None, template=None, signals=None, Mmats="tm",

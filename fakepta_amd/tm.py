@@ -27,6 +27,24 @@ def stack_design(Mmats):
     return M, ncol
 
 
+def design_of(psrs, Mmats, what):
+    """Mmats "tm" (each pulsar's Mmat), None (nothing marginalised) or a list of [n_p, m_p <= 16] -> (M, ncol_psr)."""
+    if isinstance(Mmats, str):
+        if Mmats != "tm":
+            raise ValueError(f"{what}: Mmats must be 'tm', None or a list of matrices, got {Mmats!r}")
+        Mmats = [p.Mmat for p in psrs]
+    if Mmats is None:
+        Mmats = [np.zeros((len(p.toas), 0)) for p in psrs]
+    Mmats = list(Mmats)
+    if len(Mmats) != len(psrs):
+        raise ValueError(f"{what}: {len(Mmats)} design matrices for {len(psrs)} pulsars")
+    for i, (m, p) in enumerate(zip(Mmats, psrs)):
+        if np.ndim(m) != 2 or np.shape(m)[0] != len(p.toas):
+            raise ValueError(f"{what}: design matrix of pulsar {i} must be [{len(p.toas)}, n_col], got shape "
+                             f"{np.shape(m)}")
+    return stack_design(Mmats)
+
+
 def weights_of(psrs, weights, n_toa):
     """weights "white": 1 / (EFAC^2 toaerr^2 + EQUAD^2) of each pulsar's noisedict; None: unit weights; else an array
     [n_toa] or a list of per-pulsar arrays. ECORR is not part of the weights."""
