@@ -570,6 +570,20 @@ def likelihood_grid_array(psrs, target=None, phi=None, log10_A=None, gamma=None,
                            per_pulsar=per_pulsar, want_posterior=posterior)
 
 
+def fe_statistic_array(psrs, fgw, nside=None, sky=None, signals=None, marginalize_tm=True, weights='white',
+                       rcond=None, rcond_fe=None, per_frequency=True, full=False):
+    """The continuous-wave F-statistics of psr.residuals for a whole array in ONE GPU call (not in the reference): the
+    Earth-term Fe-statistic on the frequencies fgw and the directions of a HEALPix map of nside (or sky [n, 2] of
+    (cos_gwtheta, gwphi), add_cgw's keywords) with its maxima, and the incoherent Fp-statistic per frequency. The noise
+    model is what the pulsars carry, as optimal_statistic_array takes it (a common process as each pulsar's auto-term).
+    Returns a dict: Fe_max, argmax, cos_gwtheta_ml, gwphi_ml, fgw_ml, Fe_f, argmax_f, Fp, fap_max and on request the map
+    Fe (fakepta_amd.fe.derive, R = 1). ECORR is not part of the weights. residuals and signal_model are untouched."""
+    from fakepta_amd import fe as _fe
+    return _fe.statistic_array(psrs, fgw, nside=nside, sky=sky, signals=signals,
+                               Mmats='tm' if marginalize_tm else None, weights=weights, rcond=rcond,
+                               rcond_fe=rcond_fe, per_frequency=per_frequency, full=full)
+
+
 def fit_timing_model_array(psrs, weights='white', rcond=None):
     """Pulsar.fit_timing_model for a whole array in ONE GPU call. weights: 'white', None, an array over all TOAs or a
     list of per-pulsar arrays. Returns the ranks [P]."""

@@ -68,6 +68,13 @@ _SIGS = [
     ("fpta_batch_lnl", _c_int, [_ctx_p, _vp, _vp, _vp]),
     ("fpta_lnl_grid", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp,
                                _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fpta_batch_set_fe", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _dbl, _i32,
+                                   _vp, _i32, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    ("fpta_batch_fe_info", _c_int, [_ctx_p, _vp]),
+    ("fpta_batch_fe", _c_int, [_ctx_p, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fpta_fe_statistic", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
+                                   _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_white_accumulate", _c_int, [_ctx_p, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_gp_covariance", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_noise_wiener", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -155,6 +162,7 @@ TM_MAX_COL = 16  # columns of one pulsar's design matrix (fpta_tm_project, fpta_
 FIT_MAX_COMP, FIT_MAX_COEF = 4, 512  # components and Fourier columns of one fit (fpta_batch_set_fit)
 OS_MAX_COMP, OS_MAX_COL, OS_MAX_COEF = 8, 1024, 512  # components, all Fourier columns, the target's (fpta_batch_set_os)
 LNL_MAX_COEF, LNL_MAX_GRID = 256, 4096  # the target's Fourier columns and the grid points (fpta_batch_set_lnl)
+FE_MAX_COMP, FE_MAX_FREQ, FE_MAX_SKY, FE_MAX_PSR = 7, 256, 12288, 256  # fpta_batch_set_fe's limits
 ORF_PLAN_LEN = 10  # FPTA_ORF_PLAN_LEN
 ORF_PLAN_KEYS = ("tile", "chunk", "map_group", "n_tiles", "n_chunks", "n_split", "chunks_per_split", "n_groups",
                  "groups_per_launch", "workspace_bytes")
@@ -709,20 +717,11 @@ class Context:
                                                _ptr(res), _ptr(coef), _ptr(rank), _ptr(kept)), "fpta_fit_coefficients")
         return coef, rank, kept.astype(bool)
 
-    @classmethod
-    def _os_args(cls, what, P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G):
-        """The tables of an optimal-statistic call as contiguous arrays of the C types: the component tables as
-        _fit_args makes them (up to OS_MAX_COMP components, OS_MAX_COL columns), phi [P, sum N_c] (a row [sum N_c] is
-        repeated), masks None or uint8 [C, n] (an entry None: the component acts everywhere), phi_hat [N_target], G
-        [J, P, P]."""
-        n_modes, f, idx, freqf, common = cls._fit_args(what, P, n_modes, f, idx, freqf, OS_MAX_COMP, OS_MAX_COL)
+    @staticmethod
+    def _phi_mask_args(what, P, n, n_modes, phi, masks):
+        """phi [P, sum N_c] (a row [sum N_c] is repeated) and masks None or uint8 [C, n] (an entry None: the component
+        acts everywhere) of a noise model whose component tables _fit_args has made."""
         n_f = int(n_modes.sum())
-        target = int(target)
-        if not 0 <= target < len(n_modes):
-            raise ValueError(f"{what}: target component {target} outside [0, {len(n_modes)})")
-        if 2 * int(n_modes[target]) > OS_MAX_COEF:
-            raise ValueError(f"{what}: the target has {2 * int(n_modes[target])} Fourier columns, more than "
-                             f"{OS_MAX_COEF}")
         phi = _f64(phi)
         if phi.shape == (n_f,):
             phi = np.ascontiguousarray(np.tile(phi, (P, 1)))
@@ -739,6 +738,30 @@ class Context:
                     if m.shape != (n,):
                         raise ValueError(f"{what}: the mask of component {c} must hold {n} flags, got {m.shape}")
                     mask[c] = m != 0
+        return phi, mask
+
+    @classmethod
+    def _noise_args(cls, what, P, n, n_modes, f, idx, freqf, phi, masks):
+        """A noise model without a target as contiguous arrays of the C types: the component tables as _fit_args makes
+        them (up to OS_MAX_COMP components, OS_MAX_COL columns), then _phi_mask_args. Returns (n_modes, f, idx, freqf,
+        common, phi, mask)."""
+        n_modes, f, idx, freqf, common = cls._fit_args(what, P, n_modes, f, idx, freqf, OS_MAX_COMP, OS_MAX_COL)
+        phi, mask = cls._phi_mask_args(what, P, n, n_modes, phi, masks)
+        return n_modes, f, idx, freqf, common, phi, mask
+
+    @classmethod
+    def _os_args(cls, what, P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G):
+        """The tables of an optimal-statistic call as contiguous arrays of the C types: the component tables as
+        _fit_args makes them (up to OS_MAX_COMP components, OS_MAX_COL columns), phi and masks as _phi_mask_args makes
+        them, phi_hat [N_target], G [J, P, P]."""
+        n_modes, f, idx, freqf, common = cls._fit_args(what, P, n_modes, f, idx, freqf, OS_MAX_COMP, OS_MAX_COL)
+        target = int(target)
+        if not 0 <= target < len(n_modes):
+            raise ValueError(f"{what}: target component {target} outside [0, {len(n_modes)})")
+        if 2 * int(n_modes[target]) > OS_MAX_COEF:
+            raise ValueError(f"{what}: the target has {2 * int(n_modes[target])} Fourier columns, more than "
+                             f"{OS_MAX_COEF}")
+        phi, mask = cls._phi_mask_args(what, P, n, n_modes, phi, masks)
         phi_hat = _f64(phi_hat)
         if phi_hat.shape != (int(n_modes[target]),):
             raise ValueError(f"{what}: the template must hold {int(n_modes[target])} values, got {phi_hat.shape}")
@@ -882,6 +905,108 @@ class Context:
                                        n_vec, _ptr(res), _ptr(d), _ptr(q), _ptr(X), _ptr(rank), _ptr(ld), _ptr(U)),
                     "fpta_lnl_grid")
         return d, q, X, rank, ld, U
+
+    @classmethod
+    def _fe_args(cls, what, P, n, n_modes, f, idx, freqf, phi, masks, fgw, sky, pos):
+        """The tables of an F-statistic call: the noise model as _noise_args makes it (up to FE_MAX_COMP components;
+        none: n_modes None or empty), fgw [G], sky [n_sky, 2] = (cos_gwtheta, gwphi) and pos [P, 3] within the library's
+        limits."""
+        if n_modes is None or len(n_modes) == 0:
+            n_modes, f, idx, freqf, common, phi, mask = np.zeros(0, dtype=np.int32), None, None, None, True, None, None
+        else:
+            if len(n_modes) > FE_MAX_COMP:
+                raise ValueError(f"{what}: {len(n_modes)} components, more than {FE_MAX_COMP}")
+            n_modes, f, idx, freqf, common, phi, mask = cls._noise_args(what, P, n, n_modes, f, idx, freqf, phi, masks)
+        fgw = np.atleast_1d(_f64(fgw))
+        if fgw.ndim != 1 or not 1 <= len(fgw) <= FE_MAX_FREQ:
+            raise ValueError(f"{what}: fgw must hold 1 .. {FE_MAX_FREQ} frequencies, got shape {fgw.shape}")
+        sky = _f64(sky)
+        if sky.ndim != 2 or sky.shape[1] != 2 or not 1 <= len(sky) <= FE_MAX_SKY:
+            raise ValueError(f"{what}: sky must be [n_sky, 2] with 1 .. {FE_MAX_SKY} directions, got {sky.shape}")
+        pos = _f64(pos)
+        if pos.shape != (P, 3):
+            raise ValueError(f"{what}: pos must be [{P}, 3], got {pos.shape}")
+        if P > FE_MAX_PSR:
+            raise ValueError(f"{what}: {P} pulsars, more than {FE_MAX_PSR}")
+        return n_modes, f, idx, freqf, common, phi, mask, fgw, sky, pos
+
+    @staticmethod
+    def _fe_tables(P, G, n_sky, want):
+        return ((np.zeros((2 * n_sky, P)), np.zeros((n_sky, G, 10)), np.zeros((P, G, 3)), np.zeros(G, dtype=np.int32))
+                if want else (None, None, None, None))
+
+    def batch_set_fe(self, n_modes, f, idx, freqf, phi, fgw, sky, pos, masks=None, M=None, ncol_psr=None, weights=None,
+                     rcond=None, rcond_fe=None, tables=False, clear=False):
+        """The F-statistics of the batch layout (fpta_batch_set_fe): the noise model as batch_set_os takes it (without a
+        target), the frequencies fgw [G], the directions sky [n_sky, 2] = (cos_gwtheta, gwphi) and the pulsars' unit
+        vectors pos [P, 3]. clear=True clears it. Returns (kept columns of M [P], dict(F [2 n_sky, P], Minv [n_sky, G,
+        10], minv [P, G, 3], n_eff [G]) or None without tables)."""
+        info = self.batch_info()
+        P, n = info["n_psr"], info["n_toa"]
+        rank = np.zeros(P, dtype=np.int32)
+        if P == 0 or clear:  # without a layout: the library's own state error
+            self._check(_lib.fpta_batch_set_fe(self._h, 0, None, None, 1, None, None, None, None, 0, None, None, None,
+                                               0.0, 0, None, 0, None, None, 0.0, _ptr(rank), None, None, None, None),
+                        "fpta_batch_set_fe")
+            return rank, None
+        if n_modes is None or len(n_modes) == 0:
+            raise ValueError("batch_set_fe: the noise model needs a component (one with phi = 0 for white noise only)")
+        n_modes, f, idx, freqf, common, phi, mask, fgw, sky, pos = self._fe_args(
+            "batch_set_fe", P, n, n_modes, f, idx, freqf, phi, masks, fgw, sky, pos)
+        M, ncol_psr, weights, rcond = self._tm_args("batch_set_fe", P, n, M, ncol_psr, weights, rcond)
+        F, Minv, minv, neff = self._fe_tables(P, len(fgw), len(sky), tables)
+        self._check(_lib.fpta_batch_set_fe(self._h, len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx),
+                                           _ptr(freqf), _ptr(phi), _ptr(mask), M.shape[1], _ptr(M), _ptr(ncol_psr),
+                                           _ptr(weights), rcond, len(fgw), _ptr(fgw), len(sky), _ptr(sky), _ptr(pos),
+                                           0.0 if rcond_fe is None else float(rcond_fe), _ptr(rank), _ptr(F),
+                                           _ptr(Minv), _ptr(minv), _ptr(neff)), "fpta_batch_set_fe")
+        return rank, (dict(F=F, Minv=Minv, minv=minv, n_eff=neff) if tables else None)
+
+    def batch_fe_info(self):
+        """K, G and n_sky of the F-statistics that are set (0: none) and the realizations of the last result
+        (fpta_batch_fe_info)."""
+        return dict(zip(("K", "G", "n_sky", "n_real"), self._info4(_lib.fpta_batch_fe_info, "fpta_batch_fe_info")))
+
+    @staticmethod
+    def _fe_out(P, K, G, n_sky, R, per_frequency, full, coefficients):
+        return dict(Fe_max=np.zeros(R), argmax=np.zeros((2, R), dtype=np.int32),
+                    Fe_f=np.zeros((G, R)) if per_frequency else None,
+                    argmax_f=np.zeros((G, R), dtype=np.int32) if per_frequency else None, Fp=np.zeros((G, R)),
+                    Fe=np.zeros((n_sky, G, R)) if full else None, X=np.zeros((P, K, R)) if coefficients else None)
+
+    def batch_fe(self, per_frequency=True, full=False, coefficients=False):
+        """The F-statistics of the last block (fpta_batch_fe): a dict of Fe_max [R], argmax [2, R] (direction,
+        frequency), Fe_f and argmax_f [G, R] (or None), Fp [G, R], Fe [n_sky, G, R] (the map, or None) and X [P, K, R]
+        (or None). The buffers are sized from the library's own K, G and n_sky."""
+        have, R = self.batch_fe_info(), self._block_real()
+        o = self._fe_out(self.batch_info()["n_psr"], have["K"], have["G"], have["n_sky"], R, per_frequency, full,
+                         coefficients)
+        self._check(_lib.fpta_batch_fe(self._h, _ptr(o["Fe_max"]), _ptr(o["argmax"]), _ptr(o["Fe_f"]),
+                                       _ptr(o["argmax_f"]), _ptr(o["Fp"]), _ptr(o["Fe"]), _ptr(o["X"])),
+                    "fpta_batch_fe")
+        return o
+
+    def fe_statistic(self, offs, toas, nu, n_modes, f, idx, freqf, phi, fgw, sky, pos, res, masks=None, M=None,
+                     ncol_psr=None, weights=None, rcond=None, rcond_fe=None, per_frequency=True, full=False,
+                     coefficients=False, tables=False):
+        """The F-statistics of every row of res [n_vec, n_toa] or [n_toa] for any array (fpta_fe_statistic). Returns
+        (batch_fe's dict with R = n_vec, kept columns of M [P], batch_set_fe's tables or None)."""
+        offs, toas, nu, res, P, n, n_vec = self._oneshot_args("fe_statistic", offs, toas, nu, res)
+        n_modes, f, idx, freqf, common, phi, mask, fgw, sky, pos = self._fe_args(
+            "fe_statistic", P, n, n_modes, f, idx, freqf, phi, masks, fgw, sky, pos)
+        M, ncol_psr, weights, rcond = self._tm_args("fe_statistic", P, n, M, ncol_psr, weights, rcond)
+        G, S = len(fgw), len(sky)
+        o = self._fe_out(P, 2 * G, G, S, n_vec, per_frequency, full, coefficients)
+        rank = np.zeros(P, dtype=np.int32)
+        F, Minv, minv, neff = self._fe_tables(P, G, S, tables)
+        self._check(_lib.fpta_fe_statistic(self._h, P, _ptr(offs), _ptr(toas), _ptr(nu), len(n_modes), _ptr(n_modes),
+                                           _ptr(f), int(common), _ptr(idx), _ptr(freqf), _ptr(phi), _ptr(mask),
+                                           M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights), rcond, G, _ptr(fgw), S,
+                                           _ptr(sky), _ptr(pos), 0.0 if rcond_fe is None else float(rcond_fe), n_vec,
+                                           _ptr(res), _ptr(o["Fe_max"]), _ptr(o["argmax"]), _ptr(o["Fe_f"]),
+                                           _ptr(o["argmax_f"]), _ptr(o["Fp"]), _ptr(o["Fe"]), _ptr(o["X"]), _ptr(rank),
+                                           _ptr(F), _ptr(Minv), _ptr(minv), _ptr(neff)), "fpta_fe_statistic")
+        return o, rank, (dict(F=F, Minv=Minv, minv=minv, n_eff=neff) if tables else None)
 
     def batch_clear(self):
         self._check(_lib.fpta_batch_clear_signals(self._h), "fpta_batch_clear_signals")

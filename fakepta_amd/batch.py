@@ -17,6 +17,7 @@ import numpy as np
 from . import _capi
 from . import fit as _fit
 from . import lnl as _lnl
+from . import fe as _fe
 from . import os as _os
 from . import tm as _tm
 from fakepta.correlated_noises import orf_factor, orf_matrix
@@ -73,6 +74,7 @@ class BatchSimulator:
         self._fit = None  # set_fourier_fit: dict(n_modes, f, idx, freqf, common)
         self._os = None  # set_optimal_statistic: dict(G, nab, n_orf, centres, counts, target, template)
         self._lnl = None  # set_likelihood_grid: dict(phi, axes, ld, target)
+        self._fe = None  # set_fe_statistic: dict(fgw, sky, n_eff)
         self.segments = []  # (name, kind, f, amp, idx, L, mask) — host copy for checking/reporting
         names = signals
         if names is None:
@@ -405,6 +407,55 @@ class BatchSimulator:
         o = self._lnl
         d, q, _ = self.ctx.batch_lnl(per_pulsar=per_pulsar)
         return _lnl.derive(d, o["axes"], o["ld"], q, posterior)
+
+    # ------------------------------------------------------------------ continuous-wave F-statistics
+    def set_fe_statistic(self, fgw, nside=None, sky=None, noise="layout", Mmats="tm", weights="white", rcond=None,
+                         rcond_fe=None):
+        """Set the continuous-wave detection statistics that fe_statistic() applies to a block: per realization the
+        Earth-term Fe-statistic on a grid of sky directions and frequencies, Fe = N^T M^-1 N / 2 (2 Fe is chi^2 with 4
+        degrees of freedom under the null), and the incoherent Fp-statistic per frequency (the definition of
+        include/fakepta_amd.h; the antenna patterns are add_cgw's). Returns the kept design columns [P].
+
+        fgw:      the gravitational-wave frequencies [G <= 256] in Hz, neither harmonics nor ordered.
+        nside:    the directions are the pixel centres of a HEALPix RING map (12 nside^2 <= 12288), or
+        sky:      an explicit array [n, 2] of (cos_gwtheta, gwphi), add_cgw's keywords.
+        noise:    "layout": every signal of this layout (f, amp^2, idx, mask) makes P_p, a common process as each
+                  pulsar's auto-term; or a list of such segments. A layout without a Gaussian process is white noise.
+        Mmats, weights, rcond: as set_fourier_fit; the design is marginalised with infinite variance.
+        rcond_fe: a (direction, frequency) whose scaled M has a Cholesky pivot <= rcond_fe (default 1e-10) is singular
+                  and reads NaN.
+
+        Every pulsar needs pos. The weights are diagonal: ECORR is not part of them. The pulsar term and an evolving
+        frequency are not modelled."""
+        segs = self.segments if isinstance(noise, str) and noise == "layout" else noise
+        if isinstance(segs, str):
+            raise ValueError(f"set_fe_statistic: noise must be 'layout' or a list of segments, got {noise!r}")
+        fgw, sky = _fe.check_frequencies(fgw), _fe.sky_grid(nside, sky)
+        model = _fe.model_of(segs, len(self.psrs))
+        pos = _fe.positions_of(self.psrs, "set_fe_statistic")
+        M, ncol = _os.design_of(self.psrs, Mmats, "set_fe_statistic")
+        w = _tm.weights_of(self.psrs, weights, self.n_toa)
+        self._fe = None
+        rank, tab = self.ctx.batch_set_fe(model["n_modes"], model["f"], model["idx"], model["freqf"], model["phi"], fgw,
+                                          sky, pos, masks=model["masks"], M=M, ncol_psr=ncol, weights=w, rcond=rcond,
+                                          rcond_fe=rcond_fe, tables=True)
+        self._fe = dict(fgw=fgw, sky=sky, n_eff=tab["n_eff"])
+        return rank
+
+    def fe_statistic(self, per_frequency=True, full=False):
+        """The F-statistics of every realization of the last block, computed on the device; the block is untouched. A
+        dict: Fe_max [R] with argmax [2, R] (direction, frequency; -1 where every point is singular) and
+        cos_gwtheta_ml, gwphi_ml, fgw_ml [R]; Fe_f and argmax_f [G, R] (the maximum over the directions per frequency;
+        None with per_frequency=False); Fp [G, R] with n_eff [G] (2 Fp is chi^2 with 2 n_eff degrees of freedom); Fe
+        [n_sky, G, R], the whole map, with full=True; fap_max = fe.false_alarm(Fe_max); the grids fgw and sky. Per batch
+        of a sharded job: simulate_sharded(..., on_batch=lambda sim, first, n: (sim.add_cgw(src),
+        ...sim.fe_statistic()...))."""
+        if getattr(self, "_fe", None) is None:
+            raise ValueError("fe_statistic: no F-statistic is set; call set_fe_statistic() first")
+        o = self._fe
+        out = _fe.derive(self.ctx.batch_fe(per_frequency=per_frequency, full=full), o["fgw"], o["sky"])
+        out["n_eff"] = o["n_eff"]
+        return out
 
     def synth_from_z(self, z):
         """Validation mode: z [n_real, n_seg, P, N_max, 2] standard normals (cos, sin)."""

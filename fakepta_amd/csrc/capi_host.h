@@ -169,8 +169,8 @@ struct Layout {
   }
 };
 
-// The consumers of the block that fpta_batch_synth leaves on the device (tm.hip, fit.hip, os.hip, lnl.hip). A slot owns
-// the device tables and results of one feature: the context holds one for the batch layout and one for the feature's
+// The consumers of the block that fpta_batch_synth leaves on the device (tm.hip, fit.hip, os.hip, lnl.hip, fe.hip). A slot
+// owns the device tables and results of one feature: the context holds one for the batch layout and one for the feature's
 // one-shot call. A state says what the batch slot holds (set: the feature is set; R, rpad: the realizations of its last
 // result, 0: none, and their padding); it is all zero while the feature is not set, and fpta_batch_set_toas clears it.
 
@@ -225,6 +225,20 @@ struct LnlState {
   void clear() { *this = LnlState(); }
 };
 
+// Continuous-wave F-statistics: k_fit_apply's fourth operator slot (B_p with the frequency grid as rows, X), the antenna
+// table in k_fe_sky's tile layout [tiles of 8 directions][k-steps of 4 pulsars][64 lanes], M^-1 [n_sky][G][10], m^-1
+// [P][G][3] and the results Fe_f / arg [G][rpad], Fe_max / arg [rpad] (the argmax as direction and frequency), Fp
+// [G][rpad] and, when asked for, the map [n_sky][G][rpad]
+struct FeSlot {
+  FitSlot x;
+  DevBuf f, minv, pinv, fef, argf, femax, argmax, fp, map;
+};
+struct FeState {
+  bool set = false;
+  int32_t K = 0, G = 0, n_sky = 0, R = 0, rpad = 0;  // K = 2 G: the cosine rows, then the sine rows
+  void clear() { *this = FeState(); }
+};
+
 }  // namespace capi
 
 using namespace capi;
@@ -263,8 +277,9 @@ struct fpta_ctx {
   int64_t orf_split = 0;  // FPTA_OPT_ORF_SPLIT: 0 auto (fpta_orf::make_plan), n >= 1 forces n K-splits
   // The consumers of the resident block, each with the slot of the batch layout, the slot of its one-shot call and the
   // state of the former: the timing-model projection (tm.hip), the Fourier fit (fit.hip; cross_rows the cosine / sine
-  // row of every mode and cross_x the cross-spectra of one fpta_batch_fit_cross), the optimal statistic (os.hip) and
-  // the likelihood grid (lnl.hip). res1: the residuals of a one-shot call, which ends with the stream idle.
+  // row of every mode and cross_x the cross-spectra of one fpta_batch_fit_cross), the optimal statistic (os.hip), the
+  // likelihood grid (lnl.hip) and the continuous-wave F-statistics (fe.hip). res1: the residuals of a one-shot call,
+  // which ends with the stream idle.
   TmSlot tm, tm1;
   TmState tm_st;
   FitSlot fit, fit1;
@@ -274,6 +289,8 @@ struct fpta_ctx {
   OsState os_st;
   LnlSlot lnl, lnl1;
   LnlState lnl_st;
+  FeSlot fe, fe1;
+  FeState fe_st;
   DevBuf res1;
   // a new layout: every table above is per TOA of the layout it was set for, and the last results go with them
   void clear_consumers() {
@@ -281,6 +298,7 @@ struct fpta_ctx {
     fit_st.clear();
     os_st.clear();
     lnl_st.clear();
+    fe_st.clear();
   }
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;

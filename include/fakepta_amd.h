@@ -479,6 +479,90 @@ int fpta_lnl_grid(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const doubl
                   const double* phi_grid, int32_t n_vec, const double* res /* [n_vec][n_toa_total] */, double* dlnl,
                   double* q_psr, double* X, int32_t* rank_out, double* ld_out, double* U_out);
 
+/* Continuous-wave F-statistics: per realization of a block the Earth-term Fe-statistic of a circular binary on a grid
+ * of directions and frequencies, with its maxima, and the incoherent Fp-statistic per frequency (Babak & Sesana 2012;
+ * Ellis, Siemens & Creighton 2012; added without a change of FPTA_VERSION: no existing call changes). This text is the
+ * specification.
+ * The inputs are the optimal statistic's (above) without a target, a template and pair weights: weights w > 0, a
+ * nuisance design M_p [n_p][m_p <= 16] marginalised with infinite variance under the timing-model projection's rank
+ * rule, C <= 7 Gaussian-process components with prior variances phi [n_psr][sum_c N_c] >= 0, all of them noise (a
+ * common process enters as each pulsar's auto-term):
+ *   P_p = W^-1 + sum_c F_c Phi_c F_c^T + M_p inf M_p^T,   (x|y)_p = x^T P_p^-1 y.
+ * New inputs: G frequencies fgw [G] > 0, 1 <= G <= 256, neither harmonics nor ordered; n_sky directions sky
+ * [n_sky][2] = (cos theta_s, phi_s), 1 <= n_sky <= 12288; the pulsars' unit vectors pos [n_psr][3], n_psr <= 256.
+ * With s_g(t) = sin 2 pi f_g t and c_g(t) = cos 2 pi f_g t at the pulsar's TOAs, per pulsar and frequency
+ *   x_pg = [(r_p|s_g), (r_p|c_g)] per realization,   m_pg = [[(s|s), (s|c)], [(s|c), (c|c)]].
+ * The antenna patterns of pulsar p for direction s are fpta_cw_accumulate's: m = (sin phi, -cos phi, 0), n = (-cos th
+ * cos phi, -cos th sin phi, sin th), Om = (-sin th cos phi, -sin th sin phi, -cos th), F+ = ((m.p)^2 - (n.p)^2) / (2 (1
+ * + Om.p)), Fx = (m.p)(n.p) / (1 + Om.p), so an injected source and the statistic agree on the convention.
+ *   N(s, g) = [sum_p F+ x_s, sum_p F+ x_c, sum_p Fx x_s, sum_p Fx x_c],
+ *   M(s, g) = sum_p [[F+^2, F+ Fx], [F+ Fx, Fx^2]] (x) m_pg   (4 x 4),
+ *   Fe[s][g][r] = N^T M^-1 N / 2      (the omega^(-1/3) of the literature's basis cancels),
+ *   Fp[g][r] = sum_p x_pg^T m_pg^-1 x_pg / 2, summed in pulsar order.
+ * 2 Fe is chi^2 with 4 degrees of freedom under the null and has non-centrality (h|h) under a source at (s, g); 2 Fp
+ * is chi^2 with 2 n_eff[g] degrees of freedom. The pulsar term, an evolving frequency, the maximum-likelihood
+ * amplitudes M^-1 N and ECORR in the weights are out of scope.
+ * A pulsar whose column lies in the span of its marginalised model, (s|s) <= rcond^2 s^T W s or the same for c (the
+ * timing-model rank rule's threshold; 1 / yr beside annual design columns, say), drops out at that frequency: its two
+ * rows of B_p and its m_pg are exactly zero.
+ * The inverses are made on the host in long double: the matrix is scaled to unit diagonal and factored by Cholesky;
+ * a diagonal entry that is not positive and finite, or a pivot (the diagonal of the scaled Schur complement, before
+ * its square root) <= rcond_fe (<= 0: 1e-10), makes the point singular; else the inverse is D^-1/2 L^-T L^-1 D^-1/2
+ * with L^-1 by forward substitution, rounded once to fp64. A direction for which 1 + Om.p is exactly zero for some
+ * pulsar is singular at every frequency and that pulsar's F+ and Fx read 0 in the table. A singular (s, g) has Fe =
+ * NaN (with one pulsar every point is singular). A pulsar whose m_pg is singular (no TOAs, say) adds nothing to Fp,
+ * its m^-1 reads 0, and n_eff[g] counts the others.
+ * Reductions: Fe_f[g][r] = max_s Fe with its argmax, Fe_max[r] = max_g Fe_f with its (s, g). NaN never wins a maximum,
+ * ties go to the lower index (for Fe_max: the lower frequency, then that frequency's direction), all-NaN gives NaN and
+ * index -1.
+ * On the host (long double, sums in index order): B_p [K = 2 G][n_p] with row g = c_g^T P_p^-1 and row G + g = s_g^T
+ * P_p^-1, by the optimal statistic's orthogonalisation with the frequency grid appended as a common achromatic target
+ * with phi = 0 (every row takes the projection form), rounded once to fp64; m_pg from the unrounded B_p; the antenna
+ * table F [2 n_sky][n_psr] (row 2 s: F+, row 2 s + 1: Fx), M and M^-1 [n_sky][G][10] (the upper triangle row by row:
+ * 00 01 02 03 11 12 13 22 23 33) and m^-1 [n_psr][G][3] = (ss, sc, cc), each rounded once. The device computes X [n_psr]
+ * [K][n_real] = B_p r with the Fourier fit's kernel (k_fit_apply) on a fourth operator slot with its own coefficient
+ * buffer, N on fp64 MFMA with k = the pulsars in order (k_fe_sky: the quadratic form, the map and the maximum over the
+ * directions per lane, merged in a fixed order, no atomics) and Fp and the maximum over the frequencies in k_fe_reduce.
+ * A realization's numbers are bit-identical whatever the number of realizations, its position among them and its
+ * neighbours. The block is read only. Validated on the host before anything is uploaded or launched (FPTA_EINVAL):
+ * everything the optimal statistic refuses of these inputs (the frequency grid counts as component C), C > 7, n_psr >
+ * 256, G outside [1, 256], n_sky outside [1, 12288], a frequency that is not positive and finite, a cos theta outside
+ * [-1, 1], a phi that is not finite, a position that is not a unit vector to 1e-6 (the message names the frequency,
+ * direction or pulsar). A failed allocation is FPTA_ENOMEM with the size in the message. Kernel time is booked under
+ * FPTA_K_DENSE, one entry per call.
+ *
+ * fpta_batch_set_fe: the statistics of the batch layout (after fpta_batch_set_toas, else FPTA_ESTATE). rank_out (NULL
+ *   or [n_psr]) gets the kept columns of M_p; F_out (NULL or [2 n_sky][n_psr]), Minv_out (NULL or [n_sky][G][10]),
+ *   minv_out (NULL or [n_psr][G][3]) and neff_out (NULL or [G]) the host tables. n_comp == 0 clears it (a model without
+ *   a process passes one component with phi = 0), and so does fpta_batch_set_toas. Independent of the timing model,
+ *   the Fourier fit, the optimal statistic and the likelihood grid.
+ * fpta_batch_fe_info: info[0] = K of the statistics that are set (0: none), info[1] = G, info[2] = n_sky, info[3] =
+ *   the realizations of the last fpta_batch_fe result (0: none).
+ * fpta_batch_fe: the statistics of the context's last block on the context's stream (FPTA_ESTATE without a block or
+ *   without statistics set). Each output may be NULL: fe_max [n_real]; arg_max [2][n_real] (row 0 the direction, row
+ *   1 the frequency); fe_f and arg_f [G][n_real]; fp [G][n_real]; fe_map [n_sky][G][n_real] (written on the device only
+ *   when asked for: 8 n_sky G n_real bytes); X [n_psr][K][n_real].
+ * fpta_fe_statistic: one call for any array and n_vec residual vectors res [n_vec][offs[n_psr]], independent of the
+ *   batch layout. A pulsar may have no TOAs; n_comp may be 0 (white noise only). */
+int fpta_batch_set_fe(fpta_ctx* ctx, int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                      const double* idx, const double* freqf, const double* phi /* [n_psr][sum_c N_c] */,
+                      const uint8_t* mask /* NULL or [n_comp][n_toa_total] */, int32_t n_col,
+                      const double* M /* [n_toa_total][n_col] */, const int32_t* ncol_psr, const double* weights,
+                      double rcond, int32_t n_fgw, const double* fgw, int32_t n_sky, const double* sky /* [n_sky][2] */,
+                      const double* pos /* [n_psr][3] */, double rcond_fe, int32_t* rank_out, double* F_out,
+                      double* Minv_out, double* minv_out, int32_t* neff_out);
+int fpta_batch_fe_info(fpta_ctx* ctx, int64_t* info /* [4] */);
+int fpta_batch_fe(fpta_ctx* ctx, double* fe_max, int32_t* arg_max, double* fe_f, int32_t* arg_f, double* fp,
+                  double* fe_map, double* X);
+int fpta_fe_statistic(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const double* toas, const double* nu,
+                      int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                      const double* idx, const double* freqf, const double* phi, const uint8_t* mask, int32_t n_col,
+                      const double* M, const int32_t* ncol_psr, const double* weights, double rcond, int32_t n_fgw,
+                      const double* fgw, int32_t n_sky, const double* sky, const double* pos, double rcond_fe,
+                      int32_t n_vec, const double* res /* [n_vec][n_toa_total] */, double* fe_max, int32_t* arg_max,
+                      double* fe_f, int32_t* arg_f, double* fp, double* fe_map, double* X, int32_t* rank_out,
+                      double* F_out, double* Minv_out, double* minv_out, int32_t* neff_out);
+
 /* Replaces fakepta/fake_pta.py:201-230 (add_white_noise), with ECORR fixed (defects D1/D2):
  *   residuals[t] += sigma[t] * z[t]  +  sum over blocks b containing t: ecorr_sigma[b] * zb[b]
  * Blocks are CSR: block_offs[n_blocks+1] into block_idx (TOA indices, any order).
@@ -812,7 +896,8 @@ int fpta_build_flags(void);
                         * (fpta_batch_fit, fpta_fit_coefficients, fpta_batch_fit_cross); fpta_orf_anisotropic: one entry per
                           launch batch (k_orf_aniso + k_orf_reduce); fpta_batch_os, fpta_os_statistic: one entry per
                           call (k_fit_apply + k_os_pairs + k_os_reduce); fpta_batch_lnl, fpta_lnl_grid: one entry per
-                          call (k_fit_apply + k_lnl_quad + k_lnl_reduce) */
+                          call (k_fit_apply + k_lnl_quad + k_lnl_reduce); fpta_batch_fe, fpta_fe_statistic: one entry per
+                          call (k_fit_apply + k_fe_sky + k_fe_reduce) */
 #define FPTA_K_GRID 5  /* gridded path: real-DFT grid values (k_grid_dft); its interpolation counts as SYNTH */
 #define FPTA_K_CW 6    /* fpta_cw_accumulate: one entry per call (k_cw_prep + k_cw_main [+ k_cw_reduce]);
                         * fpta_batch_cw_accumulate: one entry per call (k_cw_block, or those kernels + k_cw_bcast) */
