@@ -318,11 +318,11 @@ static int stream_checksums(fpta_multi* m, uint64_t seed, int64_t real0, int64_t
 int fpta_multi_synth(fpta_multi* m, uint64_t seed, int64_t real0, int64_t n_real, int32_t batch,
                      double* checksums_out) {
   if (!m) return fail(nullptr, FPTA_EINVAL, "null multi");
-  if (n_real <= 0 || real0 < 0 || batch <= 0 || !checksums_out) {
+  if (n_real <= 0 || batch <= 0 || !checksums_out) {
     m->err = "multi_synth: bad arguments";
     return fail(nullptr, FPTA_EINVAL, m->err);
   }
-  if (real0 + n_real > ((int64_t)1 << 32)) {
+  if (real0 < 0 || real0 > ((int64_t)1 << 32) || n_real > ((int64_t)1 << 32) - real0) {
     m->err = "multi_synth: realization index exceeds the 32-bit Philox counter word";
     return fail(nullptr, FPTA_EINVAL, m->err);
   }
@@ -419,9 +419,8 @@ int fpta_comm_gather(fpta_comm* m, const double* send, int64_t count, double* re
 int fpta_batch_synth_checksums(fpta_ctx* c, uint64_t seed, int64_t real0, int64_t n_real, int32_t batch,
                                double* sums) {
   if (!c) return fail(nullptr, FPTA_EINVAL, "null ctx");
-  if (n_real <= 0 || real0 < 0 || batch <= 0 || !sums)
-    return fail(c, FPTA_EINVAL, "batch_synth_checksums: bad arguments");
-  if (real0 + n_real > ((int64_t)1 << 32))
+  if (n_real <= 0 || batch <= 0 || !sums) return fail(c, FPTA_EINVAL, "batch_synth_checksums: bad arguments");
+  if (real0 < 0 || real0 > ((int64_t)1 << 32) || n_real > ((int64_t)1 << 32) - real0)
     return fail(c, FPTA_EINVAL, "batch_synth_checksums: realization index exceeds the 32-bit Philox counter word");
   fpta_multi one;
   one.ctx.push_back(c);

@@ -639,7 +639,10 @@ int fpta_batch_clear_signals(fpta_ctx* ctx);
 /* Synthesize realizations real0 .. real0+n_real-1 into the context's device buffer
  * [n_real][n_toa_total]. If out != NULL the result is also copied to host memory
  * (row-major, same shape). coeffs_out: NULL or host [n_psr][K][n_real] coefficient dump
- * (K = fpta_batch_info column count) for validation. */
+ * (K = fpta_batch_info column count) for validation. seed: any 64-bit value (the Philox key).
+ * 0 <= real0 and real0 + n_real <= 2^32 here, in fpta_batch_synth_checksums and in fpta_multi_synth
+ * (FPTA_EINVAL "realization index exceeds the 32-bit Philox counter word" otherwise, the resident
+ * block untouched); fpta_noise_draw takes real0 + n_real <= 2^33. */
 int fpta_batch_synth(fpta_ctx* ctx, uint64_t seed, int64_t real0, int32_t n_real, double* out,
                      double* coeffs_out);
 /* Validation mode: same as fpta_batch_synth but the standard normals come from the host:
