@@ -570,6 +570,20 @@ def likelihood_grid_array(psrs, target=None, phi=None, log10_A=None, gamma=None,
                            per_pulsar=per_pulsar, want_posterior=posterior)
 
 
+def correlated_likelihood_array(psrs, target=None, orfs=('hd', 'curn'), phi=None, log10_A=None, gamma=None,
+                                signals=None, marginalize_tm=True, weights='white', rcond=None, posterior=False):
+    """The Gaussian log-likelihood ratio of psr.residuals on a grid of spectra of the target process with the process
+    correlated between the pulsars by each of `orfs`, for a whole array in ONE GPU call (not in the reference):
+    dlnL[o][g] = ln p(r | Gamma_o, phi_g) - ln p(r | phi = 0) with the timing model marginalised. The noise model and
+    the grid are likelihood_grid_array's; orfs are names orf_matrix knows or [P, P] arrays. Returns a dict: dlnL,
+    argmax, lnB per ORF, lnB_vs_curn when 'curn' is among the ORFs, the axes and on request the posterior
+    (fakepta_amd.clnl.derive, R = 1). ECORR is not part of the weights. residuals and signal_model are untouched."""
+    from fakepta_amd import clnl as _clnl
+    return _clnl.grid_array(psrs, target=target, orfs=orfs, phi=phi, log10_A=log10_A, gamma=gamma, signals=signals,
+                            Mmats='tm' if marginalize_tm else None, weights=weights, rcond=rcond,
+                            want_posterior=posterior)
+
+
 def fe_statistic_array(psrs, fgw, nside=None, sky=None, signals=None, marginalize_tm=True, weights='white',
                        rcond=None, rcond_fe=None, per_frequency=True, full=False):
     """The continuous-wave F-statistics of psr.residuals for a whole array in ONE GPU call (not in the reference): the

@@ -75,6 +75,12 @@ _SIGS = [
     ("fpta_fe_statistic", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
                                    _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fpta_batch_set_clnl", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _dbl,
+                                     _i32, _vp, _i32, _vp, _vp, _vp]),
+    ("fpta_batch_clnl_info", _c_int, [_ctx_p, _vp]),
+    ("fpta_batch_clnl", _c_int, [_ctx_p, _vp, _vp, _vp, _vp]),
+    ("fpta_clnl_grid", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp,
+                                _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_white_accumulate", _c_int, [_ctx_p, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_gp_covariance", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_noise_wiener", _c_int, [_ctx_p, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -162,6 +168,7 @@ TM_MAX_COL = 16  # columns of one pulsar's design matrix (fpta_tm_project, fpta_
 FIT_MAX_COMP, FIT_MAX_COEF = 4, 512  # components and Fourier columns of one fit (fpta_batch_set_fit)
 OS_MAX_COMP, OS_MAX_COL, OS_MAX_COEF = 8, 1024, 512  # components, all Fourier columns, the target's (fpta_batch_set_os)
 LNL_MAX_COEF, LNL_MAX_GRID = 256, 4096  # the target's Fourier columns and the grid points (fpta_batch_set_lnl)
+CLNL_MAX_ORF, CLNL_MAX_N, CLNL_BUDGET = 8, 16384, 32 << 30  # ORFs, n = P K and cached bytes (fpta_batch_set_clnl)
 FE_MAX_COMP, FE_MAX_FREQ, FE_MAX_SKY, FE_MAX_PSR = 7, 256, 12288, 256  # fpta_batch_set_fe's limits
 ORF_PLAN_LEN = 10  # FPTA_ORF_PLAN_LEN
 ORF_PLAN_KEYS = ("tile", "chunk", "map_group", "n_tiles", "n_chunks", "n_split", "chunks_per_split", "n_groups",
@@ -905,6 +912,81 @@ class Context:
                                        n_vec, _ptr(res), _ptr(d), _ptr(q), _ptr(X), _ptr(rank), _ptr(ld), _ptr(U)),
                     "fpta_lnl_grid")
         return d, q, X, rank, ld, U
+
+    @classmethod
+    def _clnl_args(cls, what, P, n, n_modes, f, idx, freqf, phi, masks, target, phi_grid, A):
+        """The tables of a correlated-likelihood call: _lnl_args' and the ORF factors A [n_orf, P, P] (one [P, P] is
+        one ORF) within the library's limits."""
+        out = cls._lnl_args(what, P, n, n_modes, f, idx, freqf, phi, masks, target, phi_grid)
+        A = _f64(A)
+        if A.ndim == 2:
+            A = A[None]
+        if A.ndim != 3 or A.shape[1:] != (P, P):
+            raise ValueError(f"{what}: the ORF factors must be [n_orf, {P}, {P}], got {A.shape}")
+        if not 1 <= len(A) <= CLNL_MAX_ORF:
+            raise ValueError(f"{what}: {len(A)} ORFs outside [1, {CLNL_MAX_ORF}]")
+        return out + (np.ascontiguousarray(A),)
+
+    def batch_set_clnl(self, n_modes, f, idx, freqf, phi, target, phi_grid, A, masks=None, M=None, ncol_psr=None,
+                       weights=None, rcond=None):
+        """The correlated likelihood grid of the batch layout (fpta_batch_set_clnl): batch_set_lnl's arguments and the
+        ORF factors A [n_orf, P, P] (A A^T = Gamma). n_modes None or empty clears it. Returns (kept columns of M [P],
+        ld [n_orf, G])."""
+        info = self.batch_info()
+        P, n = info["n_psr"], info["n_toa"]
+        rank = np.zeros(P, dtype=np.int32)
+        if P == 0 or n_modes is None or len(n_modes) == 0:  # without a layout: the library's own state error
+            self._check(_lib.fpta_batch_set_clnl(self._h, 0, None, None, 1, None, None, None, None, 0, 0, None, None,
+                                                 None, 0.0, 0, None, 0, None, _ptr(rank), None), "fpta_batch_set_clnl")
+            return rank, np.zeros((0, 0))
+        n_modes, f, idx, freqf, common, phi, mask, target, phi_grid, A = self._clnl_args(
+            "batch_set_clnl", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_grid, A)
+        M, ncol_psr, weights, rcond = self._tm_args("batch_set_clnl", P, n, M, ncol_psr, weights, rcond)
+        ld = np.zeros((len(A), len(phi_grid)))
+        self._check(_lib.fpta_batch_set_clnl(self._h, len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx),
+                                             _ptr(freqf), _ptr(phi), _ptr(mask), target, M.shape[1], _ptr(M),
+                                             _ptr(ncol_psr), _ptr(weights), rcond, len(phi_grid), _ptr(phi_grid),
+                                             len(A), _ptr(A), _ptr(rank), _ptr(ld)), "fpta_batch_set_clnl")
+        return rank, ld
+
+    def batch_clnl_info(self):
+        """K, G and n_orf of the correlated likelihood grid that is set (0: none) and the realizations of the last
+        result (fpta_batch_clnl_info)."""
+        return dict(zip(("K", "G", "n_orf", "n_real"), self._info4(_lib.fpta_batch_clnl_info, "fpta_batch_clnl_info")))
+
+    def batch_clnl(self, quadratic=False, mixed=False, coefficients=False):
+        """The correlated likelihood grid of the last block (fpta_batch_clnl): (dlnL [n_orf, G, R], q [n_orf, G, R] or
+        None, V [n_orf, P K, R] or None, X [P, K, R] or None). The buffers are sized from the library's own K, G and
+        n_orf."""
+        have, R = self.batch_clnl_info(), self._block_real()
+        P = self.batch_info()["n_psr"]
+        d = np.empty((have["n_orf"], have["G"], R))
+        q = np.empty((have["n_orf"], have["G"], R)) if quadratic else None
+        V = np.empty((have["n_orf"], P * have["K"], R)) if mixed else None
+        X = np.empty((P, have["K"], R)) if coefficients else None
+        self._check(_lib.fpta_batch_clnl(self._h, _ptr(d), _ptr(q), _ptr(V), _ptr(X)), "fpta_batch_clnl")
+        return d, q, V, X
+
+    def clnl_grid(self, offs, toas, nu, n_modes, f, idx, freqf, phi, target, phi_grid, A, res, masks=None, M=None,
+                  ncol_psr=None, weights=None, rcond=None, tables=False):
+        """The correlated likelihood grid of every row of res [n_vec, n_toa] or [n_toa] for any array (fpta_clnl_grid).
+        Returns (dlnL [n_orf, G, n_vec], q [n_orf, G, n_vec], V [n_orf, P K, n_vec], X [P, K, n_vec], kept columns of M
+        [P], ld [n_orf, G], T [n_orf, P K, P K] (the plan's fp64 T) or None)."""
+        offs, toas, nu, res, P, n, n_vec = self._oneshot_args("clnl_grid", offs, toas, nu, res)
+        n_modes, f, idx, freqf, common, phi, mask, target, phi_grid, A = self._clnl_args(
+            "clnl_grid", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_grid, A)
+        M, ncol_psr, weights, rcond = self._tm_args("clnl_grid", P, n, M, ncol_psr, weights, rcond)
+        K, G, J = 2 * int(n_modes[target]), len(phi_grid), len(A)
+        d, q = np.zeros((J, G, n_vec)), np.zeros((J, G, n_vec))
+        V, X = np.zeros((J, P * K, n_vec)), np.zeros((P, K, n_vec))
+        rank, ld = np.zeros(P, dtype=np.int32), np.zeros((J, G))
+        T = np.zeros((J, P * K, P * K)) if tables else None
+        self._check(_lib.fpta_clnl_grid(self._h, P, _ptr(offs), _ptr(toas), _ptr(nu), len(n_modes), _ptr(n_modes),
+                                        _ptr(f), int(common), _ptr(idx), _ptr(freqf), _ptr(phi), _ptr(mask), target,
+                                        M.shape[1], _ptr(M), _ptr(ncol_psr), _ptr(weights), rcond, G, _ptr(phi_grid),
+                                        J, _ptr(A), n_vec, _ptr(res), _ptr(d), _ptr(q), _ptr(V), _ptr(X), _ptr(rank),
+                                        _ptr(ld), _ptr(T)), "fpta_clnl_grid")
+        return d, q, V, X, rank, ld, T
 
     @classmethod
     def _fe_args(cls, what, P, n, n_modes, f, idx, freqf, phi, masks, fgw, sky, pos):

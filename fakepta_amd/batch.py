@@ -17,6 +17,7 @@ import numpy as np
 from . import _capi
 from . import fit as _fit
 from . import lnl as _lnl
+from . import clnl as _clnl
 from . import fe as _fe
 from . import os as _os
 from . import tm as _tm
@@ -75,6 +76,7 @@ class BatchSimulator:
         self._os = None  # set_optimal_statistic: dict(G, nab, n_orf, centres, counts, target, template)
         self._lnl = None  # set_likelihood_grid: dict(phi, axes, ld, target)
         self._fe = None  # set_fe_statistic: dict(fgw, sky, n_eff)
+        self._clnl = None  # set_correlated_likelihood: dict(phi, axes, ld, names, target)
         self.segments = []  # (name, kind, f, amp, idx, L, mask) — host copy for checking/reporting
         names = signals
         if names is None:
@@ -407,6 +409,52 @@ class BatchSimulator:
         o = self._lnl
         d, q, _ = self.ctx.batch_lnl(per_pulsar=per_pulsar)
         return _lnl.derive(d, o["axes"], o["ld"], q, posterior)
+
+    # ------------------------------------------------------------------ correlated likelihood grid
+    def set_correlated_likelihood(self, target=None, orfs=("hd", "curn"), phi=None, log10_A=None, gamma=None,
+                                  noise="layout", Mmats="tm", weights="white", rcond=None):
+        """Set the ORFs and the spectrum grid that correlated_likelihood() applies to a block: per realization, ORF and
+        grid point ln p(r | Gamma_o, phi_g) - ln p(r | phi = 0) of the target process with the prior cov(a_pk, a_ql) =
+        Gamma_pq phi_k delta_kl coupling the pulsars and the timing model marginalised (the definition of
+        include/fakepta_amd.h). The device factors the coupled P K system once per (ORF, grid point) here and keeps the
+        factors (8 n_orf G (P K)^2 bytes, at most 32 GiB); a block then costs one triangular solve each. Returns the
+        kept design columns [P].
+
+        target:   as set_likelihood_grid; it needs one frequency grid for the whole array.
+        orfs:     names fakepta's orf_matrix knows ("hd", "monopole", "dipole", "curn") or explicit [P, P] arrays,
+                  symmetric positive semidefinite (ValueError otherwise); singular ORFs are fine.
+        phi, log10_A, gamma, noise, Mmats, weights, rcond: as set_likelihood_grid.
+
+        The weights are diagonal: ECORR is not part of them."""
+        segs = self.segments if isinstance(noise, str) and noise == "layout" else noise
+        if isinstance(segs, str):
+            raise ValueError(f"set_correlated_likelihood: noise must be 'layout' or a list of segments, got {noise!r}")
+        t = _os.pick_target(segs, target)
+        model = _os.noise_model(segs, len(self.psrs))
+        grid, axes = _lnl.make_grid(_lnl.target_frequencies(model, t), phi, log10_A, gamma)
+        names, _, A = _clnl.orf_factors(self.psrs, orfs, "set_correlated_likelihood")
+        M, ncol = _os.design_of(self.psrs, Mmats, "set_correlated_likelihood")
+        w = _tm.weights_of(self.psrs, weights, self.n_toa)
+        self._clnl = None
+        rank, ld = self.ctx.batch_set_clnl(model["n_modes"], model["f"], model["idx"], model["freqf"], model["phi"], t,
+                                           grid, A, masks=model["masks"], M=M, ncol_psr=ncol, weights=w, rcond=rcond)
+        self._clnl = dict(phi=grid, axes=axes, ld=ld, names=names, target=t)
+        return rank
+
+    def correlated_likelihood(self, posterior=False):
+        """The correlated likelihood grid of every realization of the last block, computed on the device; the block is
+        untouched. A dict: dlnL [n_orf, G, R] (or [n_orf, nA, ngamma, R] for a grid built from axes), per ORF argmax
+        (with axes a tuple of index arrays, and log10_A_ml, gamma_ml [n_orf, R]), lnB [n_orf, R] = logsumexp_g(dlnL) -
+        ln G, lnB_vs_curn [n_orf, R] when "curn" is among the ORFs (the row of "hd" is the Hellings-Downs versus CURN
+        Bayes factor under a uniform prior over the grid points), orfs (the names), the axes, and the normalised
+        posterior with posterior=True. Per batch of a sharded job: simulate_sharded(..., on_batch=lambda sim, first, n:
+        ...sim.correlated_likelihood()...)."""
+        if getattr(self, "_clnl", None) is None:
+            raise ValueError("correlated_likelihood: no correlated likelihood is set; call "
+                             "set_correlated_likelihood() first")
+        o = self._clnl
+        d, _, _, _ = self.ctx.batch_clnl()
+        return _clnl.derive(d, o["names"], o["axes"], o["ld"], posterior)
 
     # ------------------------------------------------------------------ continuous-wave F-statistics
     def set_fe_statistic(self, fgw, nside=None, sky=None, noise="layout", Mmats="tm", weights="white", rcond=None,

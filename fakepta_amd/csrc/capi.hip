@@ -855,33 +855,40 @@ void dense_remember(fpta_ctx* c, const DenseDims& d, int stage, int64_t ldz = 0,
   c->dn_last.ldz = ldz, c->dn_last.n_real = n_real, c->dn_last.stage = stage;
 }
 
-// In-place lower Cholesky of C (right-looking, 64-wide panels: diagonal block in LDS, panel solve,
-// MFMA trailing update). Fails with FPTA_EINVAL when C is not numerically positive definite.
-int dense_cholesky(fpta_ctx* c, const DenseDims& d) {
-  double* C = c->dn_C.as<double>();
-  const int64_t ld = d.n_pad;
-  HIPCHK(c, c->dn_PT.ensure(sizeof(double) * 64 * (size_t)d.n_pad), "dense panel alloc");
-  HIPCHK(c, c->dn_info.ensure(sizeof(int)), "dense info alloc");
-  HIPCHK(c, hipMemsetAsync(c->dn_info.p, 0, sizeof(int), c->stream), "dense info memset");
+// In-place lower Cholesky of a matrix anywhere on the device (capi_host.h)
+int dense_cholesky_at(fpta_ctx* c, double* C, int64_t ld, int64_t n, double* PT, int64_t ldp, int* info_dev,
+                      int64_t& pivot) {
+  pivot = -1;
+  HIPCHK(c, hipMemsetAsync(info_dev, 0, sizeof(int), c->stream), "dense info memset");
   {
     KTimer kt(c, FPTA_K_DENSE);
-    const int32_t T = (int32_t)((d.n + 63) / 64);
+    const int32_t T = (int32_t)((n + 63) / 64);
     for (int32_t kb = 0; kb < T; ++kb) {
       const int64_t k0 = (int64_t)kb * 64;
-      HIPCHK(c, launch_potrf_block(c->stream, C, ld, d.n, k0, c->dn_info.as<int>()), "k_potrf_block launch");
-      if (k0 + 64 >= d.n) break;
-      HIPCHK(c, launch_trsm_panel(c->stream, C, ld, d.n, k0, c->dn_PT.as<double>(), d.n_pad), "k_trsm_panel launch");
-      HIPCHK(c,
-             launch_gemm_tn(c->stream, c->dn_PT.as<double>(), d.n_pad, c->dn_PT.as<double>(), d.n_pad, false, false, C,
-                            ld, d.n, d.n, 16, 1, kb + 1, 1, nullptr),
+      HIPCHK(c, launch_potrf_block(c->stream, C, ld, n, k0, info_dev), "k_potrf_block launch");
+      if (k0 + 64 >= n) break;
+      HIPCHK(c, launch_trsm_panel(c->stream, C, ld, n, k0, PT, ldp), "k_trsm_panel launch");
+      HIPCHK(c, launch_gemm_tn(c->stream, PT, ldp, PT, ldp, false, false, C, ld, n, n, 16, 1, kb + 1, 1, nullptr),
              "k_gemm_tn (update) launch");
     }
   }
   int info = 0;
-  HIPCHK(c, hipMemcpyAsync(&info, c->dn_info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream), "dense info");
+  HIPCHK(c, hipMemcpyAsync(&info, info_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream), "dense info");
   HIPCHK(c, hipStreamSynchronize(c->stream), "dense cholesky sync");
-  if (info)
-    return fail(c, FPTA_EINVAL, "dense: covariance not positive definite (pivot " + std::to_string(info - 1) + ")");
+  if (info) pivot = info - 1;
+  return FPTA_OK;
+}
+
+// In-place lower Cholesky of the dense path's C. Fails with FPTA_EINVAL when C is not numerically positive definite.
+int dense_cholesky(fpta_ctx* c, const DenseDims& d) {
+  HIPCHK(c, c->dn_PT.ensure(sizeof(double) * 64 * (size_t)d.n_pad), "dense panel alloc");
+  HIPCHK(c, c->dn_info.ensure(sizeof(int)), "dense info alloc");
+  int64_t pivot = -1;
+  const int rc = dense_cholesky_at(c, c->dn_C.as<double>(), d.n_pad, d.n, c->dn_PT.as<double>(), d.n_pad,
+                                   c->dn_info.as<int>(), pivot);
+  if (rc) return rc;
+  if (pivot >= 0)
+    return fail(c, FPTA_EINVAL, "dense: covariance not positive definite (pivot " + std::to_string(pivot) + ")");
   return FPTA_OK;
 }
 

@@ -169,10 +169,11 @@ struct Layout {
   }
 };
 
-// The consumers of the block that fpta_batch_synth leaves on the device (tm.hip, fit.hip, os.hip, lnl.hip, fe.hip). A slot
-// owns the device tables and results of one feature: the context holds one for the batch layout and one for the feature's
-// one-shot call. A state says what the batch slot holds (set: the feature is set; R, rpad: the realizations of its last
-// result, 0: none, and their padding); it is all zero while the feature is not set, and fpta_batch_set_toas clears it.
+// The consumers of the block that fpta_batch_synth leaves on the device (tm.hip, fit.hip, os.hip, lnl.hip, fe.hip,
+// clnl.hip). A slot owns the device tables and results of one feature: the context holds one for the batch layout and
+// one for the feature's one-shot call. A state says what the batch slot holds (set: the feature is set; R, rpad: the
+// realizations of its last result, 0: none, and their padding); it is all zero while the feature is not set, and
+// fpta_batch_set_toas clears it.
 
 // A block [R][ld] of residuals on the device, rows of n_psr pulsars: the resident block, or a one-shot call's upload
 struct Block {
@@ -239,6 +240,22 @@ struct FeState {
   void clear() { *this = FeState(); }
 };
 
+// Correlated likelihood grid: k_fit_apply's fifth operator slot (B_p with the target left out of the model, X), the ORF
+// factors A [n_orf][P][P], T [n_orf][n_pad][n_pad], the scalings s [G][n_pad], the cached Cholesky factors l
+// [n_orf][G][n_pad][n_pad] with their log-determinants ld [n_orf][G] (pt, info: the factorisation's panel and info
+// word), V [n_pad][vld], the substitution's Y tiles [n_orf][G][vld / 64][n_pad][64] and the results q, d
+// [n_orf][G][rpad]
+struct ClnlSlot {
+  FitSlot x;
+  DevBuf a, t, s, l, ld, pt, info, v, y, q, d;
+};
+struct ClnlState {
+  bool set = false;
+  int32_t K = 0, G = 0, n_orf = 0, R = 0, rpad = 0;  // K = 2 N: the target's Fourier columns per pulsar
+  int64_t n = 0, n_pad = 0;                          // P K and its round-up to 64
+  void clear() { *this = ClnlState(); }
+};
+
 }  // namespace capi
 
 using namespace capi;
@@ -278,8 +295,8 @@ struct fpta_ctx {
   // The consumers of the resident block, each with the slot of the batch layout, the slot of its one-shot call and the
   // state of the former: the timing-model projection (tm.hip), the Fourier fit (fit.hip; cross_rows the cosine / sine
   // row of every mode and cross_x the cross-spectra of one fpta_batch_fit_cross), the optimal statistic (os.hip), the
-  // likelihood grid (lnl.hip) and the continuous-wave F-statistics (fe.hip). res1: the residuals of a one-shot call,
-  // which ends with the stream idle.
+  // likelihood grid (lnl.hip), the continuous-wave F-statistics (fe.hip) and the correlated likelihood grid (clnl.hip).
+  // res1: the residuals of a one-shot call, which ends with the stream idle.
   TmSlot tm, tm1;
   TmState tm_st;
   FitSlot fit, fit1;
@@ -291,6 +308,8 @@ struct fpta_ctx {
   LnlState lnl_st;
   FeSlot fe, fe1;
   FeState fe_st;
+  ClnlSlot clnl, clnl1;
+  ClnlState clnl_st;
   DevBuf res1;
   // a new layout: every table above is per TOA of the layout it was set for, and the last results go with them
   void clear_consumers() {
@@ -299,6 +318,7 @@ struct fpta_ctx {
     os_st.clear();
     lnl_st.clear();
     fe_st.clear();
+    clnl_st.clear();
   }
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
@@ -523,6 +543,13 @@ int batch_common(fpta_ctx* c, uint64_t seed, int64_t real0, int32_t n_real, cons
                  double* out, double* coeffs_out, bool white);
 int launch_block_checksums(fpta_ctx* c, bool async = false, hipStream_t* used = nullptr, double* dst = nullptr,
                            bool* direct = nullptr);
+
+// In-place lower Cholesky of the n leading rows of C (leading dimension ld, readable to the next multiple of 64;
+// right-looking, 64-wide panels: diagonal block in LDS, panel solve into PT [64][ldp], MFMA trailing update) on the ctx
+// stream, which it waits for. info_dev: the device's info word; pivot: -1, or the first non-positive pivot's row (the
+// factor is then invalid). Books one FPTA_K_DENSE entry.
+int dense_cholesky_at(fpta_ctx* c, double* C, int64_t ld, int64_t n, double* PT, int64_t ldp, int* info_dev,
+                      int64_t& pivot);
 
 // The opening of a call on the resident block, `who` the prefix of its messages. block_check refuses a null context,
 // for an injection a context without a layout ("set_toas first"), a context without a block ("nothing synthesized

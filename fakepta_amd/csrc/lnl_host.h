@@ -108,6 +108,46 @@ inline long double factor_point(int32_t K, const long double* Z, const long doub
   return 2.0L * ld;
 }
 
+// Every pulsar's operator B_p (fp64, pulsar p's [K][n_p] at K offs[p] of B) and Z_p = B_p F_p (long double, from the
+// unrounded B_p, [n_psr][K][K]) with the target left out of the base model; rows[p] = K for a pulsar with TOAs (else
+// the entry is left alone: X = 0 and Z = 0), rank[p] the kept columns of M. The pulsars are independent and write
+// disjoint parts; up to cap threads. True when one of them ran out of memory.
+inline bool build_operators(int64_t n_psr, const int64_t* offs, const double* toas, const double* nu, const Spec& sp,
+                            int64_t n_col, const double* M, const int32_t* ncol_psr, const double* weights,
+                            double rcond, int64_t cap, double* B, int32_t* rows, int32_t* rank, long double* Zall) {
+  const fpta_fit::Spec& cs = sp.comps;
+  const int64_t n_toa = n_psr > 0 ? offs[n_psr] : 0, n_f = fpta_fit::modes_of(cs);
+  const int32_t N = cs.n_modes[sp.target];
+  const int64_t K = 2 * N;
+  int32_t f0_t = 0;
+  for (int32_t c = 0; c < sp.target; ++c) f0_t += cs.n_modes[c];
+  const int64_t work_op = (2 * n_f) * (2 * n_f) * n_toa;
+  return fpta_os::run_pool(n_psr, std::min<int64_t>({cap, work_op >> 24, n_psr}), [&](int64_t p) {
+    const int64_t o = offs[p], n = offs[p + 1] - o;
+    const int32_t m = ncol_psr ? ncol_psr[p] : (int32_t)n_col;
+    if (n == 0) return;  // X = 0 and Z = 0
+    rows[(size_t)p] = (int32_t)K;
+    const double* f = cs.f + (cs.f_is_common ? 0 : p * n_f);
+    std::vector<double> phi0(sp.phi + p * n_f, sp.phi + (p + 1) * n_f), Zd((size_t)(K * K));
+    std::fill(phi0.begin() + f0_t, phi0.begin() + f0_t + N, 0.0);  // the target is not part of the base model
+    std::vector<long double> Bl((size_t)K * (size_t)n), Fk((size_t)n);
+    const uint8_t* mk = sp.mask ? sp.mask + o : nullptr;
+    rank[(size_t)p] = fpta_os::build_operator(n, toas + o, nu + o, m, M ? M + o * n_col : nullptr, n_col,
+                                              weights ? weights + o : nullptr, sp, f, phi0.data(), mk, n_toa, rcond,
+                                              B + K * o, Zd.data(), nullptr, Bl.data());
+    long double* Z = Zall + p * K * K;
+    for (int32_t j = 0; j < K; ++j) {
+      target_column(n, toas + o, nu + o, sp, f, mk, n_toa, j, Fk.data());
+      for (int32_t k = 0; k < K; ++k) {
+        const long double* row = Bl.data() + (size_t)k * (size_t)n;
+        long double s = 0.0L;
+        for (int64_t i = 0; i < n; ++i) s += row[i] * Fk[(size_t)i];
+        Z[(int64_t)k * K + j] = s;
+      }
+    }
+  });
+}
+
 // The tables of a whole array as the kernels and the callers read them
 struct Plan {
   int32_t K = 0, N = 0, G = 0;
@@ -129,15 +169,13 @@ inline int make_plan(int64_t n_psr, const int64_t* offs, const double* toas, con
                      int64_t n_grid, const double* phi_grid, Plan& plan, std::string& why, double* U_dense = nullptr) {
   if (!validate(n_psr, offs, toas, nu, sp, n_col, M, ncol_psr, weights, n_grid, phi_grid, why)) return 1;
   const fpta_fit::Spec& cs = sp.comps;
-  const int64_t n_toa = n_psr > 0 ? offs[n_psr] : 0, n_f = fpta_fit::modes_of(cs);
+  const int64_t n_toa = n_psr > 0 ? offs[n_psr] : 0;
   plan.N = cs.n_modes[sp.target];
   plan.K = 2 * plan.N;
   plan.G = (int32_t)n_grid;
   plan.u_stride = packed_size(plan.K);
   plan.max_rows = 0;
   const int64_t K = plan.K, G = n_grid;
-  int32_t f0_t = 0;
-  for (int32_t c = 0; c < sp.target; ++c) f0_t += cs.n_modes[c];
   const double bytes = 8.0 * ((double)K * (double)n_toa + (double)n_psr * (double)G * (double)(plan.u_stride + 1));
   try {
     plan.B.assign((size_t)K * (size_t)n_toa, 0.0);
@@ -154,32 +192,8 @@ inline int make_plan(int64_t n_psr, const int64_t* offs, const double* toas, con
         sg[(size_t)(g * K + k)] = std::sqrt((long double)phi_grid[g * plan.N + (k < plan.N ? k : k - plan.N)]);
     const unsigned hw = std::thread::hardware_concurrency();
     const int64_t cap = std::min<int64_t>((int64_t)(hw ? hw : 1), kPoolMax);
-    // the operators and Z: the pulsars are independent and write disjoint parts of the plan
-    const int64_t work_op = (2 * n_f) * (2 * n_f) * n_toa;
-    bool no_mem = fpta_os::run_pool(n_psr, std::min<int64_t>({cap, work_op >> 24, n_psr}), [&](int64_t p) {
-      const int64_t o = offs[p], n = offs[p + 1] - o;
-      const int32_t m = ncol_psr ? ncol_psr[p] : (int32_t)n_col;
-      if (n == 0) return;  // X = 0 and Z = 0
-      plan.rows[(size_t)p] = plan.K;
-      const double* f = cs.f + (cs.f_is_common ? 0 : p * n_f);
-      std::vector<double> phi0(sp.phi + p * n_f, sp.phi + (p + 1) * n_f), Zd((size_t)(K * K));
-      std::fill(phi0.begin() + f0_t, phi0.begin() + f0_t + plan.N, 0.0);  // the target is not part of the base model
-      std::vector<long double> Bl((size_t)K * (size_t)n), Fk((size_t)n);
-      const uint8_t* mk = sp.mask ? sp.mask + o : nullptr;
-      plan.rank[(size_t)p] = fpta_os::build_operator(n, toas + o, nu + o, m, M ? M + o * n_col : nullptr, n_col,
-                                                     weights ? weights + o : nullptr, sp, f, phi0.data(), mk, n_toa,
-                                                     rcond, plan.B.data() + K * o, Zd.data(), nullptr, Bl.data());
-      long double* Z = Zall.data() + p * K * K;
-      for (int32_t j = 0; j < K; ++j) {
-        target_column(n, toas + o, nu + o, sp, f, mk, n_toa, j, Fk.data());
-        for (int32_t k = 0; k < K; ++k) {
-          const long double* row = Bl.data() + (size_t)k * (size_t)n;
-          long double s = 0.0L;
-          for (int64_t i = 0; i < n; ++i) s += row[i] * Fk[(size_t)i];
-          Z[(int64_t)k * K + j] = s;
-        }
-      }
-    });
+    bool no_mem = build_operators(n_psr, offs, toas, nu, sp, n_col, M, ncol_psr, weights, rcond, cap, plan.B.data(),
+                                  plan.rows.data(), plan.rank.data(), Zall.data());
     if (no_mem) throw std::bad_alloc();
     // the grid: items are (pulsar, chunk of grid points)
     const int64_t chunk = 8, n_ch = (G + chunk - 1) / chunk, items = n_psr * n_ch;

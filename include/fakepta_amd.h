@@ -479,6 +479,67 @@ int fpta_lnl_grid(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const doubl
                   const double* phi_grid, int32_t n_vec, const double* res /* [n_vec][n_toa_total] */, double* dlnl,
                   double* q_psr, double* X, int32_t* rank_out, double* ld_out, double* U_out);
 
+/* Correlated likelihood grid: the likelihood grid above with the target's prior coupled between pulsars by an overlap
+ * reduction function (Hellings-Downs, monopole, dipole, any symmetric positive semidefinite Gamma), per realization of
+ * a block, per ORF and per grid point (added without a change of FPTA_VERSION: no existing call changes). This text is
+ * the specification.
+ * The inputs are the likelihood grid's, with the target's frequencies the same for every pulsar, and
+ * n_orf factors A [n_orf][n_psr][n_psr], 1 <= n_orf <= 8, each any finite matrix with A A^T = Gamma_o (the lower
+ * Cholesky factor, or a factor with zero columns for a singular ORF). The target's prior is
+ *   cov(a_pk, a_ql) = Gamma_pq phi_k delta_kl,   both quadratures of a mode sharing phi.
+ * K = 2 N, n = n_psr K <= 16384, index (p, k) = p K + k, cosine columns first. With P0_p, X_p and Z_p as above (the
+ * target left out of the base model), s_g = phi_g^(1/2) per column and D_g = diag(s_g tiled n_psr times):
+ *   T_o[(i,k),(j,l)] = sum_p A_pi A_pj Z_p[k][l]   (symmetric, independent of the grid),
+ *   V_o[(j,l)][r]    = sum_p A_pj X_p[l][r]        (independent of the grid),
+ *   C_og = I + D_g T_o D_g = L_og L_og^T   (eigenvalues >= 1),   ld[o][g] = 2 sum_i ln L_ii,
+ *   q[o][g][r] = |L_og^-1 D_g V_o[:, r]|^2,
+ *   dlnL[o][g][r] = (q[o][g][r] - ld[o][g]) / 2 = ln p(r | Gamma_o, phi_g) - ln p(r | phi = 0)
+ * with the timing model marginalised: Woodbury's identity and the matrix-determinant lemma in the symmetric form of
+ * the likelihood grid. Neither Gamma^-1 nor phi^-1 appears: modes with phi = 0 and singular ORFs need no special case,
+ * and a grid row of zeros gives exactly 0. With A = I this is the likelihood grid's dlnL.
+ * On the host, in long double with sums in index order: B_p and Z_p as for the likelihood grid; T_o summed in pulsar
+ * order from Z_p's lower triangles and rounded once to fp64, stored [n_pad][n_pad] with n_pad = n rounded up to 64 and
+ * the padding zero; s_g rounded once. At set time the device writes C_og, factors it in place with the dense path's
+ * blocked Cholesky and sums ld in index order; the factors stay cached (8 n_orf G n_pad^2 bytes, at most 32 GiB). Per
+ * block X = B_p r comes from k_fit_apply on a fifth operator slot, V from k_clnl_mix (fp64 MFMA), q from k_clnl_solve,
+ * a forward substitution blocked by 64 rows with 64 right-hand sides per workgroup on fp64 MFMA, the squares added in
+ * row order without atomics, and dlnL from k_clnl_reduce. Nothing is factored per block. A realization's results are
+ * bit-identical whatever the number of realizations, its position among them and its neighbours, and a grid point's
+ * whatever G. The block is read only. Validated on the host before anything is uploaded or launched (FPTA_EINVAL, the
+ * message names the offender): everything the likelihood grid refuses, a target whose frequencies differ between
+ * pulsars, n_orf outside [1, 8], a factor entry that is not finite, n > 16384, cached factors beyond 32 GiB (the
+ * message states the bytes). A non-positive Cholesky pivot is FPTA_EINVAL naming ORF, grid point and pivot. Beside the
+ * cached factors a call on a block of R realizations takes 8 n_orf G n_pad R' bytes of work space for the
+ * substitution's Y (R' = R rounded up to 64; 4.9 GB on 100 pulsars with K = 60, G = 100, R = 1024), sized at the call
+ * and outside that budget: a failed allocation is FPTA_ENOMEM with the size in the message. The one-shot call frees its
+ * factors and work space before it returns; the batch slot keeps them until the grid is set again or cleared. Kernel
+ * time is booked under FPTA_K_DENSE, one entry per fpta_batch_clnl call.
+ *
+ * fpta_batch_set_clnl: the grid of the batch layout (after fpta_batch_set_toas, else FPTA_ESTATE). rank_out (NULL or
+ *   [n_psr]) gets the kept columns of M_p, ld_out (NULL or [n_orf][n_grid]) ld. n_comp == 0 clears it, and so does
+ *   fpta_batch_set_toas. Independent of the other consumers of the block.
+ * fpta_batch_clnl_info: info[0] = K of the grid that is set (0: none), info[1] = G, info[2] = n_orf, info[3] = the
+ *   realizations of the last fpta_batch_clnl result (0: none).
+ * fpta_batch_clnl: the grid of the context's last block on the context's stream (FPTA_ESTATE without a block or a
+ *   grid). dlnl and q NULL or [n_orf][G][n_real], V NULL or [n_orf][n][n_real], X NULL or [n_psr][K][n_real].
+ * fpta_clnl_grid: one call for any array and n_vec residual vectors res [n_vec][offs[n_psr]], independent of the batch
+ *   layout. T_out NULL or [n_orf][n][n]: the plan's fp64 T, dense, row-major. */
+int fpta_batch_set_clnl(fpta_ctx* ctx, int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                        const double* idx, const double* freqf, const double* phi /* [n_psr][sum_c N_c] */,
+                        const uint8_t* mask /* NULL or [n_comp][n_toa_total] */, int32_t target, int32_t n_col,
+                        const double* M /* [n_toa_total][n_col] */, const int32_t* ncol_psr, const double* weights,
+                        double rcond, int32_t n_grid, const double* phi_grid /* [n_grid][N_target] */, int32_t n_orf,
+                        const double* A /* [n_orf][n_psr][n_psr] */, int32_t* rank_out, double* ld_out);
+int fpta_batch_clnl_info(fpta_ctx* ctx, int64_t* info /* [4] */);
+int fpta_batch_clnl(fpta_ctx* ctx, double* dlnl, double* q, double* V, double* X);
+int fpta_clnl_grid(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const double* toas, const double* nu,
+                   int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common, const double* idx,
+                   const double* freqf, const double* phi, const uint8_t* mask, int32_t target, int32_t n_col,
+                   const double* M, const int32_t* ncol_psr, const double* weights, double rcond, int32_t n_grid,
+                   const double* phi_grid, int32_t n_orf, const double* A, int32_t n_vec,
+                   const double* res /* [n_vec][n_toa_total] */, double* dlnl, double* q, double* V, double* X,
+                   int32_t* rank_out, double* ld_out, double* T_out);
+
 /* Continuous-wave F-statistics: per realization of a block the Earth-term Fe-statistic of a circular binary on a grid
  * of directions and frequencies, with its maxima, and the incoherent Fp-statistic per frequency (Babak & Sesana 2012;
  * Ellis, Siemens & Creighton 2012; added without a change of FPTA_VERSION: no existing call changes). This text is the
