@@ -91,6 +91,7 @@ _SIGS = [
     ("fpta_batch_set_white", _c_int, [_ctx_p, _vp, _i64, _vp, _vp, _vp]),
     ("fpta_batch_clear_signals", _c_int, [_ctx_p]),
     ("fpta_batch_synth", _c_int, [_ctx_p, _u64, _i64, _i32, _vp, _vp]),
+    ("fpta_batch_synth_spectra", _c_int, [_ctx_p, _u64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_batch_synth_from_z", _c_int, [_ctx_p, _i32, _i32, _vp, _vp]),
     ("fpta_batch_download", _c_int, [_ctx_p, _i32, _i32, _vp]),
     ("fpta_batch_device_out", _c_int, [_ctx_p, ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
@@ -1129,6 +1130,26 @@ class Context:
         co = np.empty((info["n_psr"], info["K"], n_real)) if coeffs else None
         self._check(_lib.fpta_batch_synth(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(real0), int(n_real), _ptr(out),
                                           _ptr(co)), "fpta_batch_synth")
+        return (out, co) if coeffs else out
+
+    def batch_synth_spectra(self, seed, real0, n_real, seg, form, per_pulsar, tables, to_host=True, coeffs=False):
+        """batch_synth with a spectrum per realization: table t (a float64 array whose first axis is the realization)
+        gives signal seg[t] its amplitudes (form[t] 0) or power-law parameters (form[t] 1), per_pulsar[t] 1 with a
+        pulsar axis; fakepta_amd.spectra.spectrum_tables makes the four lists. No tables: batch_synth."""
+        info = self.batch_info()
+        out = np.empty((n_real, info["n_toa"])) if to_host else None
+        co = np.empty((info["n_psr"], info["K"], n_real)) if coeffs else None
+        tables = [_f64(t) for t in tables]
+        n = len(tables)
+        if not (len(seg) == len(form) == len(per_pulsar) == n):
+            raise ValueError("batch_synth_spectra: seg, form, per_pulsar and tables must have one entry per table")
+        seg, form, per = (np.ascontiguousarray(v, dtype=np.int32).reshape(n) for v in (seg, form, per_pulsar))
+        rows = np.array([t.shape[0] if t.ndim else 0 for t in tables], dtype=np.int32)
+        ptrs = (_vp * max(n, 1))(*[t.ctypes.data for t in tables])
+        self._check(_lib.fpta_batch_synth_spectra(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(real0), int(n_real), n,
+                                                  _ptr(seg), _ptr(form), _ptr(per), _ptr(rows),
+                                                  ctypes.cast(ptrs, _vp), _ptr(out), _ptr(co)),
+                    "fpta_batch_synth_spectra")
         return (out, co) if coeffs else out
 
     def batch_synth_from_z(self, z):

@@ -158,15 +158,30 @@ class BatchSimulator:
     def n_toa(self):
         return int(self.offs[-1])
 
-    def synth(self, n_real, seed=0, real0=0, to_host=True, coeffs=False, fit=False):
+    def synth(self, n_real, seed=0, real0=0, to_host=True, coeffs=False, fit=False, spectra=None):
         """Realizations real0 .. real0+n_real-1: returns [n_real, n_toa] (host) or None (device only). fit=True removes
         the timing-model fit (set_timing_model) from the block on the device before the download: the returned array
-        and the resident block are post-fit."""
+        and the resident block are post-fit.
+
+        spectra: None, or {signal name: dict(psd=...) | dict(amp=...) | dict(log10_A=..., gamma=...)} with one row per
+        realization of this block (fakepta_amd.spectra.spectrum_tables has the shapes): realization real0 + r is drawn
+        from row r's spectrum, with the Philox draws and the operation order of the fixed-spectrum block, so a row
+        equal to the layout's amplitudes gives that block bit for bit. Signals that are not named keep the layout's
+        spectrum, and the layout itself is not modified: the next plain synth() is unchanged, and
+        set_optimal_statistic, set_likelihood_grid and the other consumers keep the layout's values as their noise
+        model whatever spectrum a block was drawn from."""
+        def run(to_host):
+            if spectra is None:
+                return self.ctx.batch_synth(seed, real0, n_real, to_host=to_host, coeffs=coeffs)
+            from . import spectra as _spectra
+            seg, form, per, tables = _spectra.spectrum_tables(self, spectra, n_real)
+            return self.ctx.batch_synth_spectra(seed, real0, n_real, seg, form, per, tables, to_host=to_host,
+                                                coeffs=coeffs)
         if not fit:
-            return self.ctx.batch_synth(seed, real0, n_real, to_host=to_host, coeffs=coeffs)
+            return run(to_host)
         if not self._has_tm:
             raise ValueError("synth(fit=True): no timing model is set; call set_timing_model() first")
-        got = self.ctx.batch_synth(seed, real0, n_real, to_host=False, coeffs=coeffs)
+        got = run(False)
         self.ctx.batch_project()
         out = self.ctx.batch_download(0, n_real) if to_host else None
         return (out, got[1]) if coeffs else out
@@ -769,7 +784,7 @@ class RcclComm:
             self.comm = None
 
 
-def simulate_sharded(sim, n_real, seed=0, real0=0, batch=4096, comm=None, on_batch=None):
+def simulate_sharded(sim, n_real, seed=0, real0=0, batch=4096, comm=None, on_batch=None, spectra=None):
     """Realizations real0 .. real0 + n_real - 1 of `sim`'s noise model over every rank of `comm`.
 
     Rank g of G synthesizes its shard [real0 + g n / G, real0 + (g + 1) n / G) (shard_bounds) in batches of
@@ -779,6 +794,12 @@ def simulate_sharded(sim, n_real, seed=0, real0=0, batch=4096, comm=None, on_bat
     on rank 0 and None on the other ranks. TOAs, tables and the ORF factor are replicated (each rank builds
     its own BatchSimulator); realization r is bit-identical whatever G and `batch` are (Philox counters carry
     the global index), which tests/test_dist_gloo.py and tests/test_gpu_c3.py check.
+
+    spectra: None, or the per-realization spectra of BatchSimulator.synth(spectra=...) for the whole job: a dict of
+    arrays whose leading axis holds the n_real realizations (row g - real0 is realization g's), or a callable
+    (first, n) -> such a dict for realizations first .. first + n - 1. Every batch takes its own rows, through the
+    per-batch loop (the library's streamed job takes no tables), so a realization is the same whatever the batch size
+    and the number of ranks.
 
     sim: BatchSimulator (or any object with synth(n, seed=, real0=, to_host=False) and checksums()).
     comm: RcclComm (GPU ranks) or RealizationComm (gloo; default: a single-rank job)."""
@@ -800,12 +821,18 @@ def simulate_sharded(sim, n_real, seed=0, real0=0, batch=4096, comm=None, on_bat
         ctx.set_option(_capi.OPT_FUSE_CHECKSUMS, 1)
         ctx.set_option(_capi.OPT_MFMA_MIN_REAL, 1)
     try:
-        if ctx is not None and on_batch is None and hi > lo:
+        looped = ctx is None or on_batch is not None or spectra is not None
+        if not looped and hi > lo:
             # no per-batch consumer: the whole shard streams inside the library, batches back to back
             sums[:] = ctx.batch_synth_checksums(seed, real0 + lo, hi - lo, batch)
-        for first in range(lo, hi, batch) if ctx is None or on_batch is not None else ():
+        for first in range(lo, hi, batch) if looped else ():
             n = min(batch, hi - first)
-            sim.synth(n, seed=seed, real0=real0 + first, to_host=False)
+            if spectra is None:
+                sim.synth(n, seed=seed, real0=real0 + first, to_host=False)
+            else:
+                from .spectra import slice_spectra
+                part = spectra(real0 + first, n) if callable(spectra) else slice_spectra(spectra, first, n)
+                sim.synth(n, seed=seed, real0=real0 + first, to_host=False, spectra=part)
             if on_batch is not None:
                 on_batch(sim, real0 + first, n)
             sums[first - lo:first - lo + n] = sim.checksums()

@@ -163,6 +163,14 @@ int layout_add_signal(fpta_ctx* c, Layout& L, int32_t kind, int32_t nm, const do
   Seg* s = new Seg();
   s->nm_orig = nm;
   for (int32_t r = 0; r < rows; ++r) s->h_w0.push_back(w[(size_t)r * nmp]);
+  s->h_amp = a;
+  s->h_fdf.assign((size_t)rows * nmp * 2, 0.0);
+  for (int32_t r = 0; r < rows; ++r)
+    for (int32_t k = 0; k < nm; ++k) {
+      const double fk = f[(size_t)r * nm + k];
+      s->h_fdf[((size_t)r * nmp + k) * 2] = fk;
+      s->h_fdf[((size_t)r * nmp + k) * 2 + 1] = fk - (k ? f[(size_t)r * nm + k - 1] : 0.0);
+    }
   if (mask) s->h_mask.assign(mask, mask + L.n_toa);
   int rc;
   if ((rc = upload(c, s->w, w.data(), sizeof(double) * w.size(), "add_signal w")) ||
@@ -367,8 +375,8 @@ int run_coefficients(fpta_ctx* c, Layout& L, uint64_t seed, int64_t real0, int32
   };
   if (nmx.valid) {
     if (nmx.layout == &L && nmx.version == L.version && nmx.seed == seed && nmx.real0 == real0 && nmx.n_real == R &&
-        nmx.R_pad == R_pad && pipe && side && merge && !zin && !x_out && !coef_host && nmx.done &&
-        nmx.seg == next_mix_seg(c, L, R_pad))
+        nmx.R_pad == R_pad && pipe && side && merge && !zin && !x_out && !coef_host && nmx.done && !c->spec.on &&
+        nmx.seg == next_mix_seg(c, L, R_pad))  // (a block with amplitude tables never takes a fixed-amplitude mix)
       nm_seg = nmx.seg;
     else if ((rc0 = next_mix_miss()))
       return rc0;
@@ -436,6 +444,8 @@ int run_coefficients(fpta_ctx* c, Layout& L, uint64_t seed, int64_t real0, int32
       fused_g[g] = 1;
       for (int32_t i : G.members[g]) in_fused[i] = 1;
     }
+  // per-realization spectra: signal i's amplitude table of this block, or null
+  auto spec_tab = [&](size_t i) { return c->spec.on ? c->spec.tab[i] : nullptr; };
   std::vector<int32_t> fuse_into(L.segs.size(), -1);
   if (merge && !defer && mfma_mix && !x_out)
     for (size_t g = 0; g < G.members.size(); ++g) {
@@ -443,7 +453,8 @@ int run_coefficients(fpta_ctx* c, Layout& L, uint64_t seed, int64_t real0, int32
       bool prefix = true;
       for (int32_t i : G.members[g]) {
         if (i == G.anchor[g]) continue;
-        prefix = prefix && L.segs[i]->d.kind == 1 && G.anchor[g] < i;
+        // (a tabled member is scaled in its own columns first: k_coef_merge adds it, and the members after it)
+        prefix = prefix && L.segs[i]->d.kind == 1 && G.anchor[g] < i && !spec_tab((size_t)i);
         if (prefix) fuse_into[i] = L.segs[G.anchor[g]]->d.col0;
       }
     }
@@ -455,7 +466,7 @@ int run_coefficients(fpta_ctx* c, Layout& L, uint64_t seed, int64_t real0, int32
   for (size_t g = 0; g < G.members.size(); ++g)
     for (int32_t i : G.members[g]) group_of[i] = (int32_t)g;
   if (pipe && use_side && c->side_split && G.built && G.ok && G.members.size() > 1 && !zin && !x_out && !coef_host &&
-      !psr) {
+      !psr && !c->spec.on) {
     int64_t best = -1;
     for (size_t g = 0; g < G.members.size(); ++g) {
       bool per_pulsar = true;
@@ -502,7 +513,9 @@ int run_coefficients(fpta_ctx* c, Layout& L, uint64_t seed, int64_t real0, int32
   };
   if (nm_seg >= 0 && !gen_mix_branch((size_t)nm_seg) && (rc0 = next_mix_miss())) return rc0;
   for (size_t i = 0; i < L.segs.size(); ++i) {
-    const SegDesc& d = L.segs[i]->d;
+    SegDesc d = L.segs[i]->d;
+    const bool tabled = spec_tab(i) != nullptr;
+    if (tabled) d.amp = c->spec_ones.as<double>();  // unit amplitudes; spectra_scale applies the table's below
     hipStream_t si = stream_of(group_of[i]);  // side2 only for members of split_g (kind 0: no mixing below)
     if (in_fused[i] && d.kind == 0) continue;  // drawn inside its grid signal's DFT
     if ((int32_t)i == nm_seg) {
@@ -546,6 +559,7 @@ int run_coefficients(fpta_ctx* c, Layout& L, uint64_t seed, int64_t real0, int32
                "k_mix launch");
     }
     }
+    if (tabled && (rc0 = spectra_scale(c, L, i, R_pad, c->coef.as<double>(), st))) return rc0;
     if (merge && !defer)
       for (size_t g = 0; g < G.members.size(); ++g)
         if (!fused_g[g] && G.members[g].size() > 1 && G.last[g] == (int32_t)i) {
@@ -567,6 +581,11 @@ int run_coefficients(fpta_ctx* c, Layout& L, uint64_t seed, int64_t real0, int32
       }
     if (st != c->stream && !pipe)
       for (size_t i = 0; i < L.segs.size(); ++i) HIPCHK(c, hipEventRecord(c->ev_sig[i], st), "event record");
+  }
+  if (c->spec.on) {  // the next tabled block rebuilds the tables after this block's last scaling
+    if (!c->ev_spec_done) HIPCHK(c, hipEventCreateWithFlags(&c->ev_spec_done, hipEventDisableTiming), "event create");
+    HIPCHK(c, hipEventRecord(c->ev_spec_done, st), "event record");
+    c->spec_done_set = true;
   }
   c->coef_side = st != c->stream && !pipe;  // pipelined: the DFT follows on the same stream, no per-signal events
   c->prev_psr = psr;
@@ -955,6 +974,11 @@ int fpta_destroy(fpta_ctx* c) {
     (void)hipStreamSynchronize(c->side2);
     (void)hipStreamDestroy(c->side2);
   }
+  if (c->spec_st) {
+    (void)hipStreamSynchronize(c->spec_st);
+    (void)hipStreamDestroy(c->spec_st);
+  }
+  if (c->ev_spec_done) (void)hipEventDestroy(c->ev_spec_done);
   if (c->red) {
     (void)hipStreamSynchronize(c->red);
     (void)hipStreamDestroy(c->red);
@@ -1515,7 +1539,8 @@ int batch_common(fpta_ctx* c, uint64_t seed, int64_t real0, int32_t n_real, cons
   } else {
     // grid signals with a per-pulsar member draw inside their DFT (not for validation draws or coefficient downloads,
     // which need every signal's coefficients in the buffer)
-    c->gen_fused = path == 4 && !zin && !coeffs_out && c->dft_gen && (c->grid_mfma & 1);
+    // (nor for a block with an amplitude table of a per-pulsar signal: a tabled signal is never drawn in a DFT)
+    c->gen_fused = path == 4 && !zin && !coeffs_out && c->dft_gen && (c->grid_mfma & 1) && !c->spec.per_pulsar;
     c->blk_real0 = real0;
     c->blk_k0 = k0;
     c->blk_k1 = k1;

@@ -62,7 +62,11 @@ struct Seg {
   int32_t nm_orig = 0;
   std::vector<double> h_w0;  // first angular frequency per row ([P] for kind 0, [1] for kind 1)
   std::vector<uint8_t> h_mask;  // host copy of the TOA mask (empty: none), for grid coalescing
-  DevBuf w, amp, L, LT, mask;
+  // per-realization spectra (spectra.hip): the amplitudes as uploaded [rows][nm] (the zero rule), and {f, delta f}
+  // [rows][nm][2] of the frequencies as given (delta f = f_k - f_{k-1}, f_{-1} = 0; padding mode: zeros), uploaded
+  // into fdf by the first power-law table of the signal
+  std::vector<double> h_amp, h_fdf;
+  DevBuf w, amp, L, LT, mask, fdf;
 };
 
 // Gridded-synthesis tables of one signal (grid.hip): real-DFT table E; its grid block starts at row rowoff of
@@ -378,6 +382,21 @@ struct fpta_ctx {
     int32_t n_real = 0;
   } last_blk;
   bool next_mix_made = false, next_mix_used = false;  // fpta_batch_grid_info_n slots 17, 18 of the last block
+  // fpta_batch_synth_spectra (spectra.hip): the current block's per-realization amplitude tables. tab[i]: signal i's
+  // table [P or 1][nm][R_pad] in spec_tab, or null (the layout's amplitudes). A tabled signal is drawn with unit
+  // amplitudes (spec_ones) and its columns are scaled by its table right after (k_spectra_scale): the amplitude stays
+  // the last factor. per_pulsar: a per-pulsar signal has a table (the block drops gen_fused). The tables are built
+  // on spec_st and the host waits for it, so they are complete before any draw is queued; ev_spec_done: the last
+  // scaling of the previous tabled block (the next build waits for it).
+  struct SpecRun {
+    bool on = false, per_pulsar = false;
+    std::vector<const double*> tab;
+  } spec;
+  DevBuf spec_raw, spec_tab, spec_ones;
+  size_t spec_ones_n = 0;
+  hipStream_t spec_st = nullptr;
+  hipEvent_t ev_spec_done = nullptr;
+  bool spec_done_set = false;
   bool coef_queued = true;  // the last run_coefficients queued work (a pipelined block that queued none: no grid-ready wait)
   int async_sums = 0;    // streamed jobs: partial-checksum reductions on their own stream (FPTA_OPT_ASYNC_SUMS; measured
                          // no faster on C3, profiles/r03h_ab_c3_async_sums.txt: the reductions then compete with the interpolation)
@@ -541,6 +560,8 @@ bool fused_layout(const fpta_ctx* c, const Layout& L);
 int32_t next_mix_seg(const fpta_ctx* c, const Layout& L, int32_t R_pad);
 int batch_common(fpta_ctx* c, uint64_t seed, int64_t real0, int32_t n_real, const double* zin, int32_t zin_nm,
                  double* out, double* coeffs_out, bool white);
+// spectra.hip: scale signal i's coefficient columns by the current block's table (after its unit-amplitude draws)
+int spectra_scale(fpta_ctx* c, const Layout& L, size_t i, int32_t R_pad, double* coef, hipStream_t st);
 int launch_block_checksums(fpta_ctx* c, bool async = false, hipStream_t* used = nullptr, double* dst = nullptr,
                            bool* direct = nullptr);
 

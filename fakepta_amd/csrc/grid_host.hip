@@ -502,7 +502,9 @@ int grid_run(fpta_ctx* c, Layout& L, SynthArgs& a, int32_t R_pad, bool pipe) {
     // real0 + this block's stride from the last one of the same seed and size when that is a whole number of blocks
     // (G ranks' interleaved blocks), else real0 + n_real.
     c->next_mix_made = false;
-    const int32_t nms = pipe && c->prev_psr ? next_mix_seg(c, L, R_pad) : -1;
+    // (a block with per-realization amplitude tables makes none; it could make the next block's fixed-amplitude mix,
+    // which is not built: the block after a tabled one runs k_gen_mix)
+    const int32_t nms = pipe && c->prev_psr && !c->spec.on ? next_mix_seg(c, L, R_pad) : -1;
     const size_t coef_bytes = sizeof(double) * (size_t)L.P * std::max(L.K, 1) * R_pad;
     const uint64_t blk_seed = (uint64_t)c->blk_k0 | ((uint64_t)c->blk_k1 << 32);
     const fpta_ctx::LastBlock& lb = c->last_blk;

@@ -706,6 +706,28 @@ int fpta_batch_clear_signals(fpta_ctx* ctx);
  * block untouched); fpta_noise_draw takes real0 + n_real <= 2^33. */
 int fpta_batch_synth(fpta_ctx* ctx, uint64_t seed, int64_t real0, int32_t n_real, double* out,
                      double* coeffs_out);
+/* fpta_batch_synth with a spectrum per realization for n_tab of the layout's signals: realization real0 + r takes the
+ * same Philox draws, in the same operation order (a z, respectively the rounded product a sum_q L[p][q] z[q]), with
+ * a from row r of the signal's table instead of from the layout. Signals without a table keep the layout's
+ * amplitudes; the layout is not modified (the next fpta_batch_synth is unchanged), and n_tab = 0 is fpta_batch_synth.
+ * Table t belongs to signal seg[t] (the id fpta_batch_add_signal returned; each at most once), holds n_rows[t] =
+ * n_real rows and is read from tables[t]:
+ *   form[t] 0, amplitudes sqrt(psd * df): [n_real][n_modes] (per_pulsar[t] 0: a common signal, or a per-pulsar signal
+ *              whose pulsars share the row) or [n_real][n_psr][n_modes] (per_pulsar[t] 1: a per-pulsar signal only),
+ *              n_modes as given to fpta_batch_add_signal;
+ *   form[t] 1, power law: (log10_A, gamma) as [n_real][2] or [n_real][n_psr][2]; the device evaluates
+ *              sqrt(powerlaw(f_k, log10_A, gamma) (f_k - f_{k-1})), f_{-1} = 0, on the signal's own frequencies
+ *              (fakepta/spectrum.py:14-17 with fyr = 1 / Julian year).
+ * A mode whose layout amplitude is exactly 0 (a pulsar without the signal, modes past a pulsar's own, the padding
+ * mode) stays 0 in every realization: form 1 writes 0 there, and so does a shared row for the pulsars it does not
+ * apply to; a form-0 entry that is nonzero where no pulsar it covers has an amplitude is an error.
+ * FPTA_EINVAL, naming the signal (and realization, pulsar, mode), with the resident block untouched: a non-finite or
+ * negative amplitude, a non-finite parameter, an unknown or repeated signal id, a per-pulsar table for a common
+ * signal, n_rows[t] != n_real. The consumers of the block (optimal statistic, likelihood grids, ...) keep the
+ * layout's amplitudes as their noise model. fpta_batch_synth_checksums and fpta_multi_synth take no tables. */
+int fpta_batch_synth_spectra(fpta_ctx* ctx, uint64_t seed, int64_t real0, int32_t n_real, int32_t n_tab,
+                             const int32_t* seg, const int32_t* form, const int32_t* per_pulsar,
+                             const int32_t* n_rows, const double* const* tables, double* out, double* coeffs_out);
 /* Validation mode: same as fpta_batch_synth but the standard normals come from the host:
  * z [n_real][n_seg][n_psr][n_modes_max][2] (cos, sin); white/ECORR are not added. */
 int fpta_batch_synth_from_z(fpta_ctx* ctx, int32_t n_real, int32_t n_modes_max, const double* z,
