@@ -5,11 +5,16 @@ and the Python surface above it, against the np.longdouble definition of tests/c
 Each stage is held to the definition applied to the device's own inputs: V to the dot-product bound from the device's
 X; q and ld to the plan's fp64 T and s, in units of n eps cond_2(C_g) q and n eps cond_2(C_g) max(1, |ld|): the
 backward error of a Cholesky factorisation and a triangular solve is a modest multiple of n eps, and it reaches q and
-ld through cond(C). Exact zeros and bit identities are compared exactly."""
+ld through cond(C). Exact zeros and bit identities are compared exactly.
+
+The cases of tests/launch_axes.py run k_clnl_mix and k_clnl_solve on three realization tiles (R = 130: vld = 192, the
+last tile with 32 padded and 32 dead columns) under the same checkers: every stage, the bit identity of the
+realizations at the tiles' edges, and a second batch block against the composed truth."""
 import numpy as np
 import pytest
 
 from tests import clnl_reference as CR
+from tests import launch_axes as AX
 from tests import lnl_reference as LR
 from tests import os_reference as OS
 from tests import test_clnl_host as CH
@@ -130,9 +135,10 @@ def check_stages(label, key, c, d, q, V, X, ld, T):
     return worst_q, worst_ld
 
 
-# (P, K, G): n = 12 (one ragged block), 70 (two blocks, the second ragged), 136 (three blocks), 256 (exactly four)
-@pytest.mark.parametrize("R", [1, 16, 33])
-@pytest.mark.parametrize("P,K,G", [(3, 4, 1), (5, 14, 3), (17, 8, 3), (4, 64, 1)])
+# (P, K, G): n = 12 (one ragged block), 70 (two blocks, the second ragged), 136 (three blocks), 256 (exactly four);
+# R = 1, 16, 33 (one realization tile) on each, and launch_axes.py's R = 130 (three tiles) on n = 12 and n = 70
+@pytest.mark.parametrize("P,K,G,R", [(P, K, G, R) for P, K, G in [(3, 4, 1), (5, 14, 3), (17, 8, 3), (4, 64, 1)]
+                                     for R in (1, 16, 33)] + [s + (AX.CLNL_R,) for s in AX.CLNL_STAGES])
 def test_every_stage_is_the_definition_applied_to_the_device_inputs(ctx, P, K, G, R):
     c = stage_case(P, K, G)
     res = np.random.default_rng(R).normal(0.0, 1e-6, (R, int(c["offs"][-1])))
@@ -171,6 +177,23 @@ def test_blocks_order_and_grid_size_do_not_change_a_bit(ctx):
     np.testing.assert_array_equal(d1[0], d[1])
     np.testing.assert_array_equal(v1[0], V[1])
     np.testing.assert_array_equal(ld1[0], ld[1])
+
+
+def test_tiles_past_the_first_do_not_change_a_bit(ctx):
+    """R = 130 on n = 70 (three realization tiles, two block rows): the realizations at the tiles' edges are the same
+    bits alone (tile 0 of a block of one) as inside the block, in X, V, q and dlnL."""
+    c = stage_case(5, 14, 3)
+    R = AX.CLNL_R
+    res = np.random.default_rng(3).normal(0.0, 1e-6, (R, int(c["offs"][-1])))
+    d, q, V, X, _, ld, _ = one_shot(ctx, c, res)
+    assert d.shape == (2, 3, R) and V.shape == (2, 70, R) and np.all(np.isfinite(d)) and np.all(q[:, [0, 2]] > 0)
+    for r in AX.CLNL_REALS:
+        d1, q1, v1, x1, _, ld1, _ = one_shot(ctx, c, np.ascontiguousarray(res[[r]]))
+        np.testing.assert_array_equal(ld1, ld)
+        np.testing.assert_array_equal(x1, X[:, :, [r]], err_msg=f"realization {r}")
+        np.testing.assert_array_equal(v1, V[:, :, [r]], err_msg=f"realization {r}")
+        np.testing.assert_array_equal(q1, q[:, :, [r]], err_msg=f"realization {r}")
+        np.testing.assert_array_equal(d1, d[:, :, [r]], err_msg=f"realization {r}")
 
 
 # ----------------------------------------------------------------------------- batch path
@@ -309,7 +332,24 @@ def test_batch_grid_end_to_end(ctx, small):
           f"the injected point {float(np.mean(flat[0, 0] - flat[1, 0])):.3f}, mean lnB_vs_curn "
           f"{float(out['lnB_vs_curn'][0].mean()):.3f}")
     assert np.all(err <= bound)
-
+    # a second block of 130 realizations: three tiles of k_clnl_mix and k_clnl_solve on the cached factors
+    R2 = AX.CLNL_R
+    try:
+        sim.synth(R2, seed=6, real0=48, to_host=False)
+        before = sim.checksums()
+        out = sim.correlated_likelihood()
+        np.testing.assert_array_equal(sim.checksums(), before)
+        assert ctx.batch_clnl_info()["n_real"] == R2 and out["dlnL"].shape == (2, 2, 2, R2)
+        flat = out["dlnL"].reshape(2, 4, R2)
+        for o in range(2):
+            np.testing.assert_array_equal(np.ravel_multi_index((out["argmax"][0][o], out["argmax"][1][o]), (2, 2)),
+                                          np.argmax(flat[o], axis=0))
+        want, bound = composed_clnl(lay, 8, ctx.batch_download(0, R2), grid, As)
+        err = np.abs(flat - want)
+        print(f"second block, R {R2}: largest error / composed bound {float(np.max(err / bound)):.3e}")
+        assert np.all(err <= bound)
+    finally:
+        sim.synth(48, seed=5, to_host=False)  # the fixture's block, for the tests after this one
 
 def test_identity_orf_is_the_likelihood_grid(ctx, small):
     """Gamma = I against likelihood_grid() of the same model on the same block, inside the sum of both paths' bounds."""

@@ -5,7 +5,8 @@ Accuracy has the rule and the margin of tests/test_gpu_cw.py: the device may be 
 the literal fp64 numpy evaluation against the 60-digit truth. Everything else is bit for bit: realization r of the
 block equals its samples plus what fpta_cw_accumulate adds to zeros for table r (in one piece for per-realization
 tables, with the default split for one shared table). The main layout is the fixture's four pulsars of 1, 63, 257 and
-70 TOAs: a one-lane slab, a partial wave, two slabs of one pulsar (256 + 1) and a slab of two waves."""
+70 TOAs: a one-lane slab, a partial wave, two slabs of one pulsar (256 + 1) and a slab of two waves. The shared table
+runs at 3 and at 17 realizations: k_cw_bcast's groups of 8 rows, one group and 8 + 8 + 1."""
 import numpy as np
 import pytest
 
@@ -173,6 +174,11 @@ def test_shared_table(ctx, capi, g, cw, sim, n_src):
     keys = ("costheta", "phi", "cosinc", "log10_mc", "log10_fgw", "log10_h", "phase0", "psi", "psrterm")
     sim.add_cgw({k: table[:, i] for i, k in enumerate(keys)})
     np.testing.assert_array_equal(ctx.batch_download(0, R), got)
+    # 17 realizations: k_cw_bcast's groups of 8 rows, two full ones and one of a single row, on two column chunks
+    R = 17
+    base = sim.synth(R, seed=12)
+    sim.add_cgw(table)
+    np.testing.assert_array_equal(ctx.batch_download(0, R), base + delay[None, :])
 
 
 def test_per_realization_distances(ctx, capi, g, cw, sim):

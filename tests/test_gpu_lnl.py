@@ -4,10 +4,16 @@ tests/lnl_reference.py.
 
 X0 = B0_p r, per pulsar and row: |got - truth| <= max(4 e_lit, (n_p + 2) eps sum_t |B_kt| |r_t|), DESIGN.md section 5i's
 rule. Stage 2 is held to the definition applied to the device's own X and the plan's own fp64 U, with the derived
-allowance of lnl_reference.quad / dlnl; exact zeros and bit identities are compared exactly."""
+allowance of lnl_reference.quad / dlnl; exact zeros and bit identities are compared exactly.
+
+The cases of tests/launch_axes.py take k_lnl_quad past its first workgroup on every launch axis (three realization
+tiles, three grid chunks, the K = 128 and K = 130 instances at their edge) under the same checkers: stage 2, the bit
+identities of realizations and grid rows at the tile and chunk edges, and a batch block of 130 realizations on a 9 x 8
+grid."""
 import numpy as np
 import pytest
 
+from tests import launch_axes as AX
 from tests import lnl_reference as LR
 from tests import os_reference as OS
 from tests import tm_reference as T
@@ -133,7 +139,8 @@ def quad_case(P, N, G, seed, empty):
 # (K % 4 = 2), 256 (16 row groups, the instance of 32 realizations); G = 1, 3, 17; R = 1, 16, 17, 33; P = 1, 2, 17
 @pytest.mark.parametrize("P,N,G,R,empty", [(1, 1, 1, 1, False), (2, 8, 3, 16, True), (17, 9, 17, 17, True),
                                            (2, 30, 3, 33, False), (2, 31, 1, 17, True), (2, 128, 3, 33, False),
-                                           (17, 1, 3, 33, True), (1, 30, 17, 1, False), (2, 128, 1, 1, False)])
+                                           (17, 1, 3, 33, True), (1, 30, 17, 1, False), (2, 128, 1, 1, False)]
+                         + AX.LNL_STAGE2)  # past one workgroup on the realization and the grid axis: launch_axes.py
 def test_stage_2_is_the_definition_applied_to_the_device_x(ctx, P, N, G, R, empty):
     c = quad_case(P, N, G, 1000 * P + 10 * N + G, empty)
     rng = np.random.default_rng(R)
@@ -165,6 +172,27 @@ def test_blocks_order_and_grid_size_do_not_change_a_bit(ctx, N):
         np.testing.assert_array_equal(ld1[:, 0], ld[:, g])
 
 
+def test_tiles_and_chunks_past_the_first_do_not_change_a_bit(ctx):
+    """N = 9, G = 70, R = 130 (three realization tiles, three grid chunks): the realizations at the tiles' edges are
+    the same bits alone (tile 0 of a block of one) as inside the block, the grid rows at the chunks' edges the same
+    alone (chunk 0, wave 0) as inside the grid."""
+    b = AX.LNL_BITWISE
+    c = quad_case(2, b["N"], b["G"], 5 + b["N"], False)
+    res = np.random.default_rng(3).normal(0.0, 1e-6, (b["R"], int(c["offs"][-1])))
+    d, q, X, _, ld, _ = one_shot(ctx, c, res)
+    assert d.shape == (b["G"], b["R"]) and np.all(np.isfinite(d)) and np.all(q[:, [0, b["G"] - 1]] > 0)
+    for r in b["reals"]:
+        d1, q1, x1, _, _, _ = one_shot(ctx, c, np.ascontiguousarray(res[[r]]))
+        np.testing.assert_array_equal(x1, X[:, :, [r]], err_msg=f"realization {r}")
+        np.testing.assert_array_equal(q1, q[:, :, [r]], err_msg=f"realization {r}")
+        np.testing.assert_array_equal(d1, d[:, [r]], err_msg=f"realization {r}")
+    for g in b["rows"]:
+        d1, q1, _, _, ld1, _ = one_shot(ctx, c, res, grid=c["grid"][g:g + 1])
+        np.testing.assert_array_equal(d1[0], d[g], err_msg=f"grid row {g}")
+        np.testing.assert_array_equal(q1[:, 0], q[:, g], err_msg=f"grid row {g}")
+        np.testing.assert_array_equal(ld1[:, 0], ld[:, g], err_msg=f"grid row {g}")
+
+
 # ----------------------------------------------------------------------------- batch path
 @pytest.fixture(scope="module")
 def small(ctx):
@@ -190,17 +218,19 @@ def composed(lay, block, grid):
     the errors y = U X inherits: e_i = sum_k (|U_ik| dX_k + dU_i (|X_k| + dX_k)) + (K + 2) eps sum_k |U_ik| |X_k|."""
     offs = lay["offs"]
     P = len(offs) - 1
-    if "per" not in _SMALL_TRUTH:
-        per = []
+    if "base" not in _SMALL_TRUTH:
+        base = []
         for p in range(P):
             sl = slice(int(offs[p]), int(offs[p + 1]))
             args = (lay["toas"][sl], lay["nu"][sl], lay["Mmats"][p], 1 / lay["sigma"][sl] ** 2, lay["comps_of"](p))
             B, Z, norms, keep = LR.base_operator(*args, lay["phis_of"](p), 1)
             phis0 = [lay["phis_of"](p)[0], np.zeros(len(lay["f_gw"]))]
-            lit = OS.operator_literal(*args, phis0, 1, keep)
-            per.append((B, lit) + LR.grid_truth(Z, grid)[:2])
-        _SMALL_TRUTH["per"] = per
-    per = _SMALL_TRUTH["per"]
+            base.append((B, OS.operator_literal(*args, phis0, 1, keep), Z))
+        _SMALL_TRUTH["base"] = base
+    key = np.asarray(grid, dtype=np.float64).tobytes()  # the factors are a grid's own: one entry per grid
+    if key not in _SMALL_TRUTH:
+        _SMALL_TRUTH[key] = [(B, lit) + LR.grid_truth(Z, grid)[:2] for B, lit, Z in _SMALL_TRUTH["base"]]
+    per = _SMALL_TRUTH[key]
     Xt, xb = OS.x_truth([q[0] for q in per], offs, block)
     lit = np.stack([per[p][1] @ block[:, offs[p]:offs[p + 1]].T for p in range(P)])
     dX = OS.x_tolerance(Xt, lit, xb)[0]
@@ -259,6 +289,46 @@ def test_batch_grid_end_to_end_and_after_project(ctx, small):
     assert np.all(np.abs(flat_p - want_p) <= bound_p)
     assert np.all(np.abs(want_p - want) <= bound)  # the definition does not see the projection
     assert np.all(np.abs(flat_p - flat) <= bound_p + bound)
+
+
+def test_batch_grid_second_block_past_one_tile_and_one_chunk(ctx, small):
+    """A second block of 130 realizations on a 9 x 8 (log10_A, gamma) grid: three realization tiles and three grid
+    chunks of k_lnl_quad<4> on the batch path, against the composed truth; the [nA, ngamma, R] result and its argmax
+    are the flat [G, R] result, amplitude slowest."""
+    from fakepta_amd import lnl
+    sim, psrs, lay = small
+    b = AX.LNL_BATCH
+    nA, ng, R = b["nA"], b["ngamma"], b["R"]
+    A = -13.6 + 0.1 * (np.arange(nA) - nA // 2)
+    gam = 13 / 3 + 0.5 * (np.arange(ng) - ng // 2)
+    rank = sim.set_likelihood_grid(log10_A=A, gamma=gam)
+    grid = sim._lnl["phi"]
+    assert list(rank) == [3] * 8 and grid.shape == (nA * ng, 5)
+    assert ctx.batch_lnl_info() == dict(K=b["K"], N=5, G=nA * ng, n_real=0)
+    for i, j in ((0, 0), (3, 7), (8, 0), (8, 7)):  # row i ngamma + j is the point (A_i, gamma_j)
+        np.testing.assert_array_equal(grid[i * ng + j], lnl.powerlaw_grid(lay["f_gw"], A[i:i + 1], gam[j:j + 1])[0])
+    sim.synth(R, seed=6, real0=48, to_host=False)
+    before = sim.checksums()
+    out = sim.likelihood_grid(per_pulsar=True)
+    np.testing.assert_array_equal(sim.checksums(), before)
+    assert ctx.batch_lnl_info()["n_real"] == R
+    assert out["dlnL"].shape == (nA, ng, R) and out["dlnL_psr"].shape == (8, nA * ng, R)
+    flat, _, _ = ctx.batch_lnl()  # the device's [G, R], as it stands
+    assert flat.shape == (nA * ng, R)
+    for i in range(nA):
+        for j in range(ng):
+            np.testing.assert_array_equal(out["dlnL"][i, j], flat[i * ng + j])
+    np.testing.assert_array_equal(np.ravel_multi_index(out["argmax"], (nA, ng)), np.argmax(flat, axis=0))
+    np.testing.assert_array_equal(out["log10_A_ml"], A[np.argmax(flat, axis=0) // ng])
+    np.testing.assert_array_equal(out["gamma_ml"], gam[np.argmax(flat, axis=0) % ng])
+    acc = np.zeros((nA * ng, R))
+    for p in range(8):
+        acc = acc + out["dlnL_psr"][p]
+    np.testing.assert_array_equal(acc, flat)
+    want, bound = composed(lay, ctx.batch_download(0, R), grid)
+    err = np.abs(flat - want)
+    print(f"second block, R {R} G {nA * ng}: largest error / composed bound {float(np.max(err / bound)):.3e}")
+    assert np.all(err <= bound)
 
 
 def test_fit_statistic_and_grid_set_together_give_their_own_results(ctx, small):

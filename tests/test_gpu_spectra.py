@@ -4,7 +4,8 @@ spectrum, with the Philox draws and the operation order of the fixed-spectrum bl
 Bit-for-bit reference: the fixed-spectrum synth on a layout rebuilt with row r as its amplitudes (code this feature
 does not touch), whose realization r must equal realization r of the tabled block. Truth: tests/spectra_reference.py
 (the oracle's normals, amplitudes per realization) at the project's tolerances (counter_space.COEF_TOL for downloaded
-coefficients, TOL / GRID_TOL of tests/test_gpu_grid.py for blocks).
+coefficients, TOL / GRID_TOL of tests/test_gpu_grid.py for blocks). test_table_kernels_past_their_first_block runs
+tests/launch_axes.py's R = 520 (three k_spectra_amp blocks, two k_spectra_scale blocks) under both.
 
 Reference semantics of one realization: /root/reference/fakepta/fake_pta.py:372-387 (per-pulsar GP),
 correlated_noises.py:153-160 (common GP), spectrum.py:12-15 (powerlaw).
@@ -14,6 +15,7 @@ import pytest
 
 from oracle import fakepta_oracle as O
 from tests import counter_space as S
+from tests import launch_axes as AX
 from tests import spectra_reference as SR
 from tests.conftest import assert_parity, rel_err
 from tests.test_gpu_grid import GRID_TOL, TOL
@@ -104,9 +106,10 @@ def _picks(R):
     return (0, R // 2 - 1 + (R // 2) % 2, R - 1)  # the first, an odd one, the last
 
 
-def _check_rows_bitwise(ctx, lay, got, seed, real0, R, rows, path=4):
-    """Realization r of `got` against the fixed-spectrum block of the layout rebuilt with rows {signal id: [R, ...]}[r]."""
-    for r in _picks(R):
+def _check_rows_bitwise(ctx, lay, got, seed, real0, R, rows, path=4, picks=None):
+    """Realization r of `got` against the fixed-spectrum block of the layout rebuilt with rows {signal id: [R, ...]}[r],
+    for r in picks (_picks(R) by default)."""
+    for r in _picks(R) if picks is None else picks:
         _build(ctx, lay, {s: v[r] for s, v in rows.items()}, path)
         want = ctx.batch_synth(seed, real0, R)
         assert np.all(np.isfinite(got[r]))
@@ -187,6 +190,80 @@ def test_per_pulsar_rows(ctx, capi, shipped):
             assert rel_err(g, want) <= GRID_TOL
             assert_parity(g, want, TOL)
         _check_rows_bitwise(ctx, lay, got2, 13, 77, R, {RN: rows})
+    finally:
+        ctx.batch_clear()
+        ctx.set_options(shipped)
+
+
+def _first_signal(co, nm, rows):
+    """[len(rows), P, nm, 2] (cos, sin) of the first signal's nm modes in a coefficient download [P][K][R]."""
+    P = co.shape[0]
+    return np.transpose(co[:, :2 * nm][:, :, list(rows)].reshape(P, nm, 2, len(rows)), (3, 0, 1, 2))
+
+
+def _device_amplitudes(z, co, radius=4):
+    """The amplitudes the device evaluated from power-law parameters agree with numpy's to COEF_TOL, not to the bit
+    (the device's pow and numpy's differ by tens of ulp), so a fixed-spectrum layout that is to give the same bits has
+    to carry the device's own. They are recovered from the tabled block's coefficients co [..., 2] = fl(a z) and the
+    unit-amplitude draws z [..., 2]: fl(co / z) is within two roundings of a, and per entry the neighbour of it within
+    `radius` ulp is taken whose products with both draws are the coefficients bit for bit (0 where the draws are 0:
+    the layout has no amplitude there). A layout that carries them stores those coefficients."""
+    live = z[..., 0] != 0.0
+    est = np.where(live, co[..., 0] / np.where(live, z[..., 0], 1.0), 0.0)
+    out, found = est.copy(), np.zeros(est.shape, dtype=bool)
+    up = dn = est
+    for _ in range(radius + 1):
+        for cand in (up, dn):
+            ok = ~found & np.all(cand[..., None] * z == co, axis=-1)
+            out[ok] = cand[ok]
+            found |= ok
+        up, dn = np.nextafter(up, np.inf), np.nextafter(dn, -np.inf)
+    assert np.all(found), f"{int(np.sum(~found))} amplitudes do not reproduce their coefficients"
+    return out
+
+
+@pytest.mark.parametrize("path", AX.SPECTRA["paths"])
+def test_table_kernels_past_their_first_block(ctx, capi, shipped, path):
+    """R = 520 from an odd real0 (R_pad = 640: three k_spectra_amp blocks, two k_spectra_scale blocks, the second a
+    quarter full) with all three signals tabled: red noise of 3 modes as per-pulsar power-law parameters (the padding
+    mode takes k_spectra_amp's k < N branch), DM as an amplitude row the pulsars share, the common signal as amplitude
+    rows. The realizations at the blocks' edges are the rebuilt fixed-spectrum layout's bit for bit, and the downloaded
+    coefficients the reference's."""
+    from fakepta import spectrum
+    c = AX.SPECTRA
+    P, R, real0, n_rn, picks = c["P"], c["R"], c["real0"], c["n_rn"], list(c["picks"])
+    lay = _make(881, P, n=c["n"], n_rn=n_rn, ragged_rn=True)
+    rng = np.random.default_rng(882)
+    rn = np.stack([rng.uniform(-14.5, -13.0, (R, P)), rng.uniform(1.0, 5.0, (R, P))], axis=2)
+    dm = np.sqrt(O.powerlaw(lay["f"][DM][:1], rng.uniform(-14.5, -13.5, (R, 1)), rng.uniform(1.0, 4.0, (R, 1))) / T)
+    gw = _gw_rows(rng, R)
+    df_rn = np.stack([O.delta_f(f) for f in lay["f"][RN]])
+    a_rn = np.sqrt(spectrum.powerlaw(lay["f"][RN][None], rn[..., :1], rn[..., 1:]) * df_rn)
+    a_rn = np.where(lay["amp"][RN][None] == 0.0, 0.0, a_rn)
+    tabs = {RN: (1, 1, rn), DM: (0, 0, dm), GW: (0, 0, gw)}
+    try:
+        segs = _build(ctx, lay, path=path)
+        got, co = _tabled(ctx, 41, real0, R, tabs, coeffs=True)
+        assert ctx.batch_grid_info()["last_path"] == path
+        want = SR.download(SR.coefficients(segs, P, 41, real0, R, {RN: a_rn, DM: dm, GW: gw}), P, R)
+        S.check_coeffs(co[:, :, picks], want[:, :, picks])
+        S.check_coeffs(co, want)  # and every realization in between
+        assert np.all(co[1:3, :2 * (n_rn + 1)] == 0.0) and np.all(co[:, 2 * n_rn:2 * (n_rn + 1)] == 0.0)
+        assert np.all(co[0, :2 * n_rn] != 0.0)
+        got2 = _tabled(ctx, 41, real0, R, tabs)  # without the download: the block's own route
+        assert ctx.batch_grid_info()["last_path"] == path and np.all(np.isfinite(got)) and np.all(np.isfinite(got2))
+        # the draws, from the layout with unit red-noise amplitudes (1 z = z), then the device's own amplitudes
+        _build(ctx, lay, {RN: (lay["amp"][RN] != 0.0).astype(np.float64)}, path)
+        _, unit = ctx.batch_synth(41, real0, R, coeffs=True)
+        a_dev = _device_amplitudes(_first_signal(unit, n_rn + 1, picks)[:, :, :n_rn],
+                                   _first_signal(co, n_rn + 1, picks)[:, :, :n_rn])
+        assert np.all((a_dev == 0.0) == (a_rn[picks] == 0.0))
+        far = np.abs(a_dev - a_rn[picks]) / np.spacing(np.maximum(a_rn[picks], 1e-300))
+        print(f"path {path}: the device's power-law amplitudes differ from numpy's by up to {far.max():.0f} ulp")
+        rows_rn = a_rn.copy()
+        rows_rn[picks] = a_dev
+        rows = {RN: rows_rn, DM: np.broadcast_to(dm[:, None, :], (R, P, N_DM)), GW: gw}
+        _check_rows_bitwise(ctx, lay, got2, 41, real0, R, rows, path, picks=picks)
     finally:
         ctx.batch_clear()
         ctx.set_options(shipped)
