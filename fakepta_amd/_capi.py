@@ -62,6 +62,9 @@ _SIGS = [
     ("fpta_batch_os", _c_int, [_ctx_p, _vp, _vp, _vp]),
     ("fpta_os_statistic", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
                                    _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fpta_batch_set_os_spectra", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp,
+                                           _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _i32, _vp]),
+    ("fpta_batch_os_spectra", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fpta_batch_set_lnl", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _dbl,
                                     _i32, _vp, _vp, _vp]),
     ("fpta_batch_lnl_info", _c_int, [_ctx_p, _vp]),
@@ -168,6 +171,7 @@ EPHEM_MSUN = 1.327124400e20 / 6.6743e-11  # FPTA_EPHEM_MSUN
 TM_MAX_COL = 16  # columns of one pulsar's design matrix (fpta_tm_project, fpta_batch_set_timing_model)
 FIT_MAX_COMP, FIT_MAX_COEF = 4, 512  # components and Fourier columns of one fit (fpta_batch_set_fit)
 OS_MAX_COMP, OS_MAX_COL, OS_MAX_COEF = 8, 1024, 512  # components, all Fourier columns, the target's (fpta_batch_set_os)
+OSS_MAX_VARY, OSS_MAX_COL = 4, 128  # varied components and their Fourier columns (fpta_batch_set_os_spectra)
 LNL_MAX_COEF, LNL_MAX_GRID = 256, 4096  # the target's Fourier columns and the grid points (fpta_batch_set_lnl)
 CLNL_MAX_ORF, CLNL_MAX_N, CLNL_BUDGET = 8, 16384, 32 << 30  # ORFs, n = P K and cached bytes (fpta_batch_set_clnl)
 FE_MAX_COMP, FE_MAX_FREQ, FE_MAX_SKY, FE_MAX_PSR = 7, 256, 12288, 256  # fpta_batch_set_fe's limits
@@ -817,6 +821,58 @@ class Context:
         X = np.empty((self.batch_info()["n_psr"], have["K"], R)) if coefficients else None
         self._check(_lib.fpta_batch_os(self._h, _ptr(Q), _ptr(Qm), _ptr(X)), "fpta_batch_os")
         return Q, Qm, X
+
+    def batch_set_os_spectra(self, n_modes, f, idx, freqf, phi, target, phi_hat, vary, vary_seg, G, n_orf, masks=None,
+                             M=None, ncol_psr=None, weights=None, rcond=None):
+        """The optimal statistic under a spectrum per realization of the batch layout (fpta_batch_set_os_spectra): the
+        noise model, target, template, design and weights as batch_set_os takes them; vary the component indices of
+        the varied set (the target last) and vary_seg the layout signal of each; the first n_orf of G [J, P, P] get a
+        joint normal matrix. n_modes None or empty clears it. Returns the kept columns of M [P]."""
+        info = self.batch_info()
+        P, n = info["n_psr"], info["n_toa"]
+        rank = np.zeros(P, dtype=np.int32)
+        if P == 0 or n_modes is None or len(n_modes) == 0:  # without a layout: the library's own state error
+            self._check(_lib.fpta_batch_set_os_spectra(self._h, 0, None, None, 1, None, None, None, None, 0, None, 0,
+                                                       None, None, 0, None, None, None, 0.0, 0, None, 0, _ptr(rank)),
+                        "fpta_batch_set_os_spectra")
+            return rank
+        n_modes, f, idx, freqf, common, phi, mask, target, phi_hat, G = self._os_args(
+            "batch_set_os_spectra", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G)
+        M, ncol_psr, weights, rcond = self._tm_args("batch_set_os_spectra", P, n, M, ncol_psr, weights, rcond)
+        vary = np.ascontiguousarray(vary, dtype=np.int32).reshape(-1)
+        vary_seg = np.ascontiguousarray(vary_seg, dtype=np.int32).reshape(-1)
+        if len(vary) != len(vary_seg):
+            raise ValueError("batch_set_os_spectra: vary and vary_seg must have one entry per varied component")
+        q = 2 * int(sum(int(n_modes[v]) for v in vary if 0 <= v < len(n_modes)))
+        if q > OSS_MAX_COL:
+            raise ValueError(f"batch_set_os_spectra: the varied set has {q} Fourier columns, more than {OSS_MAX_COL}")
+        self._check(_lib.fpta_batch_set_os_spectra(
+            self._h, len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx), _ptr(freqf), _ptr(phi), _ptr(mask),
+            target, _ptr(phi_hat), len(vary), _ptr(vary), _ptr(vary_seg), M.shape[1], _ptr(M), _ptr(ncol_psr),
+            _ptr(weights), rcond, len(G), _ptr(G), int(n_orf), _ptr(rank)), "fpta_batch_set_os_spectra")
+        return rank
+
+    def batch_os_spectra(self, seg, form, per_pulsar, tables, K, J, n_orf, per_mode=False, coefficients=False,
+                         pair_norms=False, zp=False):
+        """The statistic of the last block under the tables of batch_synth_spectra's form (fpta_batch_os_spectra): a dict
+        of Q [J, R], norm [J, R], joint [n_orf, n_orf, R] and, on request, Q_mode [J, N, R], X [P, K, R], N_ab [R, P, P]
+        (the entries a >= b) and Zp [R, P, K, K]. K, J and n_orf are those of the statistic that is set."""
+        R, P, N = self._block_real(), self.batch_info()["n_psr"], K // 2
+        tables = [_f64(t) for t in tables]
+        n = len(tables)
+        if not (len(seg) == len(form) == len(per_pulsar) == n):
+            raise ValueError("batch_os_spectra: seg, form, per_pulsar and tables must have one entry per table")
+        seg, form, per = (np.ascontiguousarray(v, dtype=np.int32).reshape(n) for v in (seg, form, per_pulsar))
+        rows = np.array([t.shape[0] if t.ndim else 0 for t in tables], dtype=np.int32)
+        ptrs = (_vp * max(n, 1))(*[t.ctypes.data for t in tables])
+        out = dict(Q=np.zeros((J, R)), norm=np.zeros((J, R)), joint=np.zeros((n_orf, n_orf, R)),
+                   Q_mode=np.zeros((J, N, R)) if per_mode else None, X=np.zeros((P, K, R)) if coefficients else None,
+                   N_ab=np.zeros((R, P, P)) if pair_norms else None, Zp=np.zeros((R, P, K, K)) if zp else None)
+        self._check(_lib.fpta_batch_os_spectra(self._h, n, _ptr(seg), _ptr(form), _ptr(per), _ptr(rows),
+                                               ctypes.cast(ptrs, _vp), _ptr(out["Q"]), _ptr(out["Q_mode"]),
+                                               _ptr(out["X"]), _ptr(out["norm"]), _ptr(out["joint"]),
+                                               _ptr(out["N_ab"]), _ptr(out["Zp"])), "fpta_batch_os_spectra")
+        return out
 
     def os_statistic(self, offs, toas, nu, n_modes, f, idx, freqf, phi, target, phi_hat, G, res, masks=None, M=None,
                      ncol_psr=None, weights=None, rcond=None):

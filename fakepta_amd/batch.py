@@ -74,6 +74,7 @@ class BatchSimulator:
         self._has_tm = False  # set_timing_model
         self._fit = None  # set_fourier_fit: dict(n_modes, f, idx, freqf, common)
         self._os = None  # set_optimal_statistic: dict(G, nab, n_orf, centres, counts, target, template)
+        self._oss = None  # set_optimal_statistic_spectra: dict(G, n_orf, centres, counts, target, template, seg, names, K)
         self._lnl = None  # set_likelihood_grid: dict(phi, axes, ld, target)
         self._fe = None  # set_fe_statistic: dict(fgw, sky, n_eff)
         self._clnl = None  # set_correlated_likelihood: dict(phi, axes, ld, names, target)
@@ -378,6 +379,85 @@ class BatchSimulator:
         o = self._os
         Q, Qm, _ = self.ctx.batch_os(per_mode=per_mode)
         return _os.derive(Q, o["G"], o["nab"], o["n_orf"], o["centres"], o["counts"], Qm)
+
+    def set_optimal_statistic_spectra(self, vary, target=None, orfs=("hd",), bins=None, template=None, noise="layout",
+                                      Mmats="tm", weights="white", rcond=None):
+        """Set the optimal statistic that optimal_statistic_spectra() applies to a block under a noise spectrum per
+        realization (fpta_batch_set_os_spectra): the statistic of set_optimal_statistic, with the prior variances of
+        the signals in `vary` taken per realization from the spectra of the call, the tables of synth(spectra=...).
+        Returns the kept design columns [P].
+
+        vary:    signal names of this layout (at most 4, at most 128 Fourier columns together); the target is added
+                 when it is not named. Every other signal of the noise model keeps its values for every realization.
+        The other arguments are set_optimal_statistic's. Independent of set_optimal_statistic, the timing model and
+        the Fourier fit: all can be set together."""
+        segs = self.segments if isinstance(noise, str) and noise == "layout" else noise
+        if isinstance(segs, str):
+            raise ValueError(f"set_optimal_statistic_spectra: noise must be 'layout' or a list of segments, got "
+                             f"{noise!r}")
+        segs = list(segs)
+        t = _os.pick_target(segs, target)
+        vary = [vary] if isinstance(vary, str) else list(vary)
+        comp, sid = [], []
+        for name in vary + [segs[t].get("name")]:
+            hit = [i for i, s in enumerate(segs) if s.get("name") == name]
+            lay = [s for s in self.segments if s["name"] == name]
+            if len(hit) != 1 or len(lay) != 1:
+                raise ValueError(f"set_optimal_statistic_spectra: {name!r} must name one signal of the layout and of "
+                                 f"the noise model (the layout has {[s['name'] for s in self.segments]})")
+            if hit[0] not in comp:
+                comp.append(hit[0])
+                sid.append(lay[0]["id"])
+        k = comp.index(t)  # the target last
+        comp.append(comp.pop(k))
+        sid.append(sid.pop(k))
+        if len(comp) > _capi.OSS_MAX_VARY:
+            raise ValueError(f"set_optimal_statistic_spectra: {len(comp)} varied signals, more than "
+                             f"{_capi.OSS_MAX_VARY}")
+        model = _os.noise_model(segs, len(self.psrs))
+        q = 2 * int(sum(model["n_modes"][c] for c in comp))
+        if q > _capi.OSS_MAX_COL:
+            raise ValueError(f"set_optimal_statistic_spectra: the varied signals have {q} Fourier columns, more than "
+                             f"{_capi.OSS_MAX_COL}")
+        phi_hat = _os.template_of(model, t, template)
+        G, n_orf, centres, counts = _os.pair_matrices(self.psrs, orfs, bins)
+        M, ncol = _os.design_of(self.psrs, Mmats, "set_optimal_statistic_spectra")
+        w = _tm.weights_of(self.psrs, weights, self.n_toa)
+        # a refused call leaves the library's statistic, and this record of it, as they were
+        rank = self.ctx.batch_set_os_spectra(model["n_modes"], model["f"], model["idx"], model["freqf"], model["phi"],
+                                             t, phi_hat, comp, sid, G, n_orf, masks=model["masks"], M=M, ncol_psr=ncol,
+                                             weights=w, rcond=rcond)
+        self._oss = dict(G=G, n_orf=n_orf, centres=centres, counts=counts, target=t, template=phi_hat, seg=sid,
+                         names=[segs[c].get("name") for c in comp], K=2 * len(phi_hat))
+        return rank
+
+    def optimal_statistic_spectra(self, spectra=None, per_mode=False, pair_norms=False):
+        """The optimal statistic of every realization of the last block, each under its own noise spectrum; the block
+        is untouched. spectra: the dict synth(spectra=...) takes (spectra.spectrum_tables), one row per realization of
+        the block, for signals of the varied set only (ValueError naming any other); a varied signal without an entry
+        takes the layout's values, None the layout's for every row. A dict: A2, snr and A2_joint [n_orf, R] (the
+        joint fit solved per realization), rho_bins [bins, R], bin_centres, bin_counts, Q [J, R], norm [J, R] and joint
+        [n_orf, n_orf, R] (the per-realization denominators), Q_mode [J, N, R] with per_mode=True and N_ab [R, P, P]
+        with pair_norms=True. An ORF or bin whose denominator is 0 in a realization is NaN there. Per batch of a
+        sharded job: on_batch=lambda sim, first, n: sim.optimal_statistic_spectra(slice_spectra(spectra, first, n))."""
+        o = getattr(self, "_oss", None)
+        if o is None:
+            raise ValueError("optimal_statistic_spectra: no statistic is set; call set_optimal_statistic_spectra() "
+                             "first")
+        seg, form, per, tables = [], [], [], []
+        if spectra:
+            from . import spectra as _spectra
+            _, _, R = self.ctx.batch_device_out()  # the library's state error without a block
+            seg, form, per, tables = _spectra.spectrum_tables(self, spectra, R)
+            for s in seg:
+                if s not in o["seg"]:
+                    name = next(g["name"] for g in self.segments if g["id"] == s)
+                    raise ValueError(f"optimal_statistic_spectra: spectra[{name!r}]: the signal is not in the varied "
+                                     f"set {o['names']}")
+        got = self.ctx.batch_os_spectra(seg, form, per, tables, o["K"], len(o["G"]), o["n_orf"], per_mode=per_mode,
+                                        pair_norms=pair_norms)
+        return _os.derive_per_realization(got["Q"], got["norm"], got["joint"], o["n_orf"], o["centres"], o["counts"],
+                                          got["Q_mode"], got["N_ab"])
 
     # ------------------------------------------------------------------ likelihood grid
     def set_likelihood_grid(self, target=None, phi=None, log10_A=None, gamma=None, noise="layout", Mmats="tm",

@@ -260,6 +260,22 @@ struct ClnlState {
   void clear() { *this = ClnlState(); }
 };
 
+// Optimal statistic under a spectrum per realization (os_spectra.hip): k_fit_apply's sixth operator slot (B0_p, z
+// [P][q][rpad]), A_p [P][q][q], the template phi_hat [N] and its square
+// roots over the K columns, the J pair-weight matrices, the call's raw tables and amplitude tables [P or 1][nm][rpad]
+// (k_spectra_amp), and the results X [P][K][rpad], Z' and N_ab of one realization chunk, the contractions
+// [J + n_orf^2][R], Q_mode [J][N][rpad], Q [J][rpad]
+struct OssSlot {
+  FitSlot x;
+  DevBuf a, phi, sph, g, raw, tab, xc, zp, nab, nrm, qm, q;
+};
+struct OssState {
+  bool set = false;
+  int32_t q = 0, K = 0, N = 0, J = 0, n_orf = 0, n_vary = 0, R = 0, rpad = 0;  // K = 2 N: the last K of the q columns
+  int32_t seg[4] = {0, 0, 0, 0};                                            // the layout signal of each varied component
+  void clear() { *this = OssState(); }
+};
+
 }  // namespace capi
 
 using namespace capi;
@@ -299,7 +315,8 @@ struct fpta_ctx {
   // The consumers of the resident block, each with the slot of the batch layout, the slot of its one-shot call and the
   // state of the former: the timing-model projection (tm.hip), the Fourier fit (fit.hip; cross_rows the cosine / sine
   // row of every mode and cross_x the cross-spectra of one fpta_batch_fit_cross), the optimal statistic (os.hip), the
-  // likelihood grid (lnl.hip), the continuous-wave F-statistics (fe.hip) and the correlated likelihood grid (clnl.hip).
+  // likelihood grid (lnl.hip), the continuous-wave F-statistics (fe.hip), the correlated likelihood grid (clnl.hip) and
+  // the optimal statistic under a spectrum per realization (os_spectra.hip; batch layout only).
   // res1: the residuals of a one-shot call, which ends with the stream idle.
   TmSlot tm, tm1;
   TmState tm_st;
@@ -314,6 +331,8 @@ struct fpta_ctx {
   FeState fe_st;
   ClnlSlot clnl, clnl1;
   ClnlState clnl_st;
+  OssSlot oss;
+  OssState oss_st;
   DevBuf res1;
   // a new layout: every table above is per TOA of the layout it was set for, and the last results go with them
   void clear_consumers() {
@@ -323,6 +342,7 @@ struct fpta_ctx {
     lnl_st.clear();
     fe_st.clear();
     clnl_st.clear();
+    oss_st.clear();
   }
   DevBuf fused_q;  // k_grid_fused's item queues: 8 per-XCD tickets + a done counter, zero between launches
   bool fused_q_ready = false;
@@ -562,6 +582,10 @@ int batch_common(fpta_ctx* c, uint64_t seed, int64_t real0, int32_t n_real, cons
                  double* out, double* coeffs_out, bool white);
 // spectra.hip: scale signal i's coefficient columns by the current block's table (after its unit-amplitude draws)
 int spectra_scale(fpta_ctx* c, const Layout& L, size_t i, int32_t R_pad, double* coef, hipStream_t st);
+// spectra.hip: k_spectra_amp for one table of signal s, already on the device as the host gave it (raw), into tab
+// [P or 1][nm][R_pad] on stream st; a power-law table uploads the signal's frequencies first
+int spectra_table(fpta_ctx* c, Seg& s, int32_t P, int32_t form, int32_t per_pulsar, const double* raw, int32_t n_real,
+                  int32_t R_pad, double* tab, hipStream_t st);
 int launch_block_checksums(fpta_ctx* c, bool async = false, hipStream_t* used = nullptr, double* dst = nullptr,
                            bool* direct = nullptr);
 
@@ -608,6 +632,11 @@ int fit_launch(fpta_ctx* c, const Block& b, int32_t K, FitSlot& s, int32_t& R_pa
 int fit_upload(fpta_ctx* c, const char* who, FitSlot& s, int32_t K, const std::vector<double>& A, int32_t n_psr,
                const int64_t* offs, const std::vector<int32_t>& rows);
 int fit_download(fpta_ctx* c, const DevBuf& coef, int64_t rows, int32_t R, int32_t R_pad, double* host);
+
+// os.hip: k_os_pairs and k_os_reduce on coefficients X [P][2 N][R_pad] (R_pad a multiple of 32), the template phi
+// [N] and J >= 1 matrices G: Q_mode into qm [J][N][R_pad], Q into q [J][R_pad]. No timer entry: the caller's spans it.
+int os_pairs_launch(fpta_ctx* c, const double* X, const double* phi, const double* G, double* qm, double* q,
+                    int32_t n_psr, int32_t N, int32_t R_pad, int32_t J);
 
 // cw_batch.hip: the one-table mode of an injection, every realization of the block getting the same delay vector.
 // bcast_vector sizes v [n_toa of the batch layout] and clears it; the caller's drop-in kernel fills it; bcast_add

@@ -162,20 +162,31 @@ static int os_launch(fpta_ctx* c, const Block& b, OsSlot& s, OsState& st) {
   const size_t b_qm = sizeof(double) * (size_t)J * (size_t)N * (size_t)R_pad, b_q = sizeof(double) * (size_t)J * R_pad;
   if (s.x.coef.ensure(b_x) != hipSuccess || s.qm.ensure(b_qm) != hipSuccess || s.q.ensure(b_q) != hipSuccess)
     return fail(c, FPTA_ENOMEM, "os: no device memory for " + std::to_string(b_x + b_qm + b_q) + " bytes of results");
-  const int jc = J <= 1 ? 1 : J <= 2 ? 2 : J <= 4 ? 4 : kOsJ;  // matrices per workgroup
-  const int64_t n_jc = (J + jc - 1) / jc;
-  if (n_jc > 65535 || N > 65535) return fail(c, FPTA_EINVAL, "os: too many pair-weight matrices or modes");
+  if ((J + kOsJ - 1) / kOsJ > 65535 || N > 65535)  // refused before the timer entry opens
+    return fail(c, FPTA_EINVAL, "os: too many pair-weight matrices or modes");
   KTimer kt(c, FPTA_K_DENSE);
   int32_t rp = 0;
   int rc = fit_launch_unbooked(c, b, K, s.x, rp);
   if (rc) return rc;
   if (rp != R_pad) return fail(c, FPTA_EINVAL, "os: k_fit_apply's realization padding changed");
   if (J == 0 || R == 0) return FPTA_OK;
+  return os_pairs_launch(c, s.x.coef.as<double>(), s.phi.as<double>(), s.g.as<double>(), s.qm.as<double>(),
+                         s.q.as<double>(), n_psr, N, R_pad, J);
+}
+
+// Stage 2 on any coefficient buffer (os_launch, and os_spectra.hip on the coefficients of its solve)
+int os_pairs_launch(fpta_ctx* c, const double* X, const double* phi, const double* G, double* qm, double* q,
+                    int32_t n_psr, int32_t N, int32_t R_pad, int32_t J) {
+  const int jc = J <= 1 ? 1 : J <= 2 ? 2 : J <= 4 ? 4 : kOsJ;  // matrices per workgroup
+  const int64_t n_jc = (J + jc - 1) / jc;
+  if (n_jc > 65535 || N > 65535) return fail(c, FPTA_EINVAL, "os: too many pair-weight matrices or modes");
+  if (R_pad % kOsRpad)
+    return fail(c, FPTA_EINVAL, "os: the coefficients' realization padding is no multiple of " + std::to_string(kOsRpad));
   OsArgs a;
-  a.X = s.x.coef.as<double>();
-  a.phi = s.phi.as<double>();
-  a.G = s.g.as<double>();
-  a.Qm = s.qm.as<double>();
+  a.X = X;
+  a.phi = phi;
+  a.G = G;
+  a.Qm = qm;
   a.P = n_psr;
   a.N = N;
   a.R_pad = R_pad;
@@ -192,8 +203,7 @@ static int os_launch(fpta_ctx* c, const Block& b, OsSlot& s, OsState& st) {
     k_os_pairs<kOsJ><<<grid, block, 0, c->stream>>>(a);
   HIPCHK(c, hipGetLastError(), "k_os_pairs launch");
   const int64_t n = (int64_t)J * R_pad;
-  k_os_reduce<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(s.qm.as<double>(), N, R_pad, n,
-                                                                            s.q.as<double>());
+  k_os_reduce<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(qm, N, R_pad, n, q);
   HIPCHK(c, hipGetLastError(), "k_os_reduce launch");
   return FPTA_OK;
 }

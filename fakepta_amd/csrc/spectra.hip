@@ -71,6 +71,20 @@ int spectra_scale(fpta_ctx* c, const Layout& L, size_t i, int32_t R_pad, double*
   return FPTA_OK;
 }
 
+int spectra_table(fpta_ctx* c, Seg& s, int32_t P, int32_t form, int32_t per_pulsar, const double* raw, int32_t n_real,
+                  int32_t R_pad, double* tab, hipStream_t st) {
+  const int32_t rows = s.d.kind == 0 ? P : 1;
+  if (form == 1 && !s.fdf.p) {
+    HIPCHK(c, s.fdf.ensure(sizeof(double) * s.h_fdf.size()), "spectra frequencies alloc");
+    HIPCHK(c, hipMemcpyAsync(s.fdf.p, s.h_fdf.data(), sizeof(double) * s.h_fdf.size(), hipMemcpyHostToDevice, st),
+           "spectra frequencies upload");
+  }
+  k_spectra_amp<<<dim3((unsigned)((R_pad + 255) / 256), (unsigned)s.d.nm, (unsigned)rows), dim3(256), 0, st>>>(
+      form, raw, per_pulsar ? P : 1, s.d.amp, s.fdf.as<double>(), s.nm_orig, s.d.nm, n_real, R_pad, tab);
+  HIPCHK(c, hipGetLastError(), "k_spectra_amp launch");
+  return FPTA_OK;
+}
+
 // The tables of one call, validated already, into c->spec: uploads, k_spectra_amp per table, and a host wait for them
 // (the tables are the caller's memory, and the draws of the block may be queued on any stream afterwards).
 static int spectra_build(fpta_ctx* c, Layout& L, int32_t n_real, int32_t R_pad, int32_t n_tab, const int32_t* seg,
@@ -114,14 +128,8 @@ static int spectra_build(fpta_ctx* c, Layout& L, int32_t n_real, int32_t R_pad, 
     double* raw = c->spec_raw.as<double>() + raw_o;
     double* tab = c->spec_tab.as<double>() + tab_o;
     HIPCHK(c, hipMemcpyAsync(raw, tables[t], sizeof(double) * len, hipMemcpyHostToDevice, st), "spectra tables upload");
-    if (form[t] == 1 && !s.fdf.p) {
-      HIPCHK(c, s.fdf.ensure(sizeof(double) * s.h_fdf.size()), "spectra frequencies alloc");
-      HIPCHK(c, hipMemcpyAsync(s.fdf.p, s.h_fdf.data(), sizeof(double) * s.h_fdf.size(), hipMemcpyHostToDevice, st),
-             "spectra frequencies upload");
-    }
-    k_spectra_amp<<<dim3((unsigned)((R_pad + 255) / 256), (unsigned)s.d.nm, (unsigned)rows), dim3(256), 0, st>>>(
-        form[t], raw, per_pulsar[t] ? P : 1, s.d.amp, s.fdf.as<double>(), s.nm_orig, s.d.nm, n_real, R_pad, tab);
-    HIPCHK(c, hipGetLastError(), "k_spectra_amp launch");
+    const int rc = spectra_table(c, s, P, form[t], per_pulsar[t], raw, n_real, R_pad, tab, st);
+    if (rc) return rc;
     c->spec.tab[(size_t)seg[t]] = tab;
     c->spec.per_pulsar = c->spec.per_pulsar || s.d.kind == 0;
     raw_o += len;

@@ -113,6 +113,52 @@ def derive(Q, G, nab, n_orf, centres=None, counts=None, Q_mode=None):
     return out
 
 
+def symmetric_pair_norms(nab):
+    """N_ab [R, P, P] as fpta_batch_os_spectra leaves it (the entries a >= b) -> symmetric with a zero diagonal, the
+    form of set_optimal_statistic's N_ab."""
+    nab = np.asarray(nab, dtype=np.float64)
+    low = np.tril(nab, -1)
+    return low + low.transpose(0, 2, 1)
+
+
+def norms_per_realization(G, nab):
+    """[J, R]: norms() of every realization's N_ab [R, P, P], row-major over the pairs a > b."""
+    il = _lower(nab.shape[1])
+    return np.array([np.sum(g[il] ** 2 * nab[:, il[0], il[1]], axis=1) for g in G]).reshape(len(G), len(nab))
+
+
+def joint_matrix_per_realization(G, nab):
+    """[J, J, R]: joint_matrix() of every realization's N_ab [R, P, P]."""
+    il = _lower(nab.shape[1])
+    rows = np.array([g[il] for g in G]).reshape(len(G), -1)
+    return np.einsum("ip,jp,rp->ijr", rows, rows, nab[:, il[0], il[1]])
+
+
+def derive_per_realization(Q, norm, joint, n_orf, centres=None, counts=None, Q_mode=None, nab=None):
+    """derive() with a denominator per realization: Q and norm [J, R], joint [n_orf, n_orf, R] (the device's, or
+    norms_per_realization / joint_matrix_per_realization). A2, snr and A2_joint [n_orf, R] (one solve per realization;
+    for one ORF it is A2), rho_bins [bins, R]; an ORF or a bin whose denominator is 0 in a realization, and a joint fit
+    whose matrix is singular there, is NaN there. Q_mode and N_ab (made symmetric) are passed through when given."""
+    Q, norm, joint = (np.asarray(v, dtype=np.float64) for v in (Q, norm, joint))
+    R = Q.shape[1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(norm > 0, Q / norm, np.nan)
+        snr = np.where(norm[:n_orf] > 0, Q[:n_orf] / np.sqrt(norm[:n_orf]), np.nan)
+    joint_a2 = np.full((n_orf, R), np.nan)
+    for r in range(R if n_orf else 0):
+        C = joint[:, :, r]
+        if np.all(np.diag(C) > 0) and np.linalg.matrix_rank(C) == n_orf:
+            joint_a2[:, r] = np.linalg.solve(C, Q[:n_orf, r])
+    out = dict(A2=ratio[:n_orf], snr=snr, A2_joint=joint_a2, rho_bins=ratio[n_orf:], Q=Q, norm=norm, joint=joint,
+               bin_centres=np.zeros(0) if centres is None else centres,
+               bin_counts=np.zeros(0, dtype=np.int64) if counts is None else counts)
+    if Q_mode is not None:
+        out["Q_mode"] = Q_mode
+    if nab is not None:
+        out["N_ab"] = symmetric_pair_norms(nab)
+    return out
+
+
 def noise_model(segments, n_psr):
     """BatchSimulator-style segments (dicts with name, kind 0 per-pulsar f, amp [P, N] / 1 common f, amp [N], idx,
     freqf, mask) -> dict(names, n_modes [C] int32, f [sum N] or [P, sum N], idx, freqf, phi [P, sum N] = amp^2, masks).

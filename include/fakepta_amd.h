@@ -423,6 +423,59 @@ int fpta_os_statistic(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const d
                       const double* res /* [n_vec][n_toa_total] */, double* Q, double* Q_mode, double* X,
                       int32_t* rank_out, double* nab_out);
 
+/* ---- optimal statistic under a noise spectrum per realization ----
+ * The statistic above with P_p of realization r built from row r of per-realization spectra, the tables of
+ * fpta_batch_synth_spectra: every realization of a block is weighted by its own noise model (a P-P run, a population
+ * prior), and one residual block under many draws of the noise parameters gives the noise-marginalised optimal
+ * statistic (added without a change of FPTA_VERSION: no existing call changes). This text is the specification.
+ * The components, the design, the weights, the target, phi_hat, X_p, Z_p, N_ab and Q are those of the optimal
+ * statistic. The components are split into a varied set V (n_vary in [1, 4] distinct component indices, the target
+ * the last of them) with q = 2 sum_{c in V} N_c <= 128 Fourier columns T_p, and the fixed rest. vary_seg[v] is the
+ * signal of the batch layout (the id fpta_batch_add_signal returned, with as many modes as the component) whose
+ * amplitudes a_r, from the call's table or else the layout's, give the varied component its prior variance
+ * phi_r = a_r^2 in realization r; the phi argument's entries of the varied components are validated and not used.
+ * With P0_p = W^-1 + sum_{c not in V} F_c Phi_c F_c^T + M_p inf M_p^T the host plans once per pulsar, in long double
+ * by the route above with the columns of V not part of the model (the projection form of a target column with
+ * phi = 0),
+ *   B0_p = T_p^T P0_p^-1  [q][n_p], rounded once to fp64, and A_p = B0_p T_p  [q][q] from the unrounded B0_p.
+ * The device computes z = B0_p r (k_fit_apply on an operator slot of its own) and per (pulsar, realization), with
+ * s = a_r over the q columns and t the target's trailing K columns,
+ *   C = I + s A_p s = L D L^T (no pivoting: C is symmetric positive definite with eigenvalues >= 1; a column with
+ *       s = 0 decouples),   W = C^-1 (s o [A_p e_t, z]),
+ *   X_k = W_kz / s_k,   Z_kj = W_kj / s_k   (from T^T P^-1 = s^-1 C^-1 s B0: no subtraction);
+ *   a target mode with s_k = 0 is not part of that realization's model and takes the projection form
+ *   X_k = z_k - sum_i A_ki s_i W_iz,   Z_kj = A_kj - sum_i A_ki s_i W_ij.
+ * Then N_ab[r] = sum_jk Z'_a,jk Z'_b,jk with Z' = phi_hat^(1/2) Z phi_hat^(1/2) for a >= b (fp64 MFMA, the K^2 entries
+ * in index order), norm[j][r] = sum_{a>b} G_j[a][b]^2 N_ab[r] for all n_g matrices and joint[j][j'][r] =
+ * sum_{a>b} G_j G_j' N_ab[r] for the first n_orf of them (row-major over a > b), and Q, Q_mode from X by the kernels
+ * of the optimal statistic. Z' takes 8 K^2 n_psr bytes per realization: the call runs in chunks of realizations, and a
+ * failed allocation is FPTA_ENOMEM with the size. Fixed operation order, no atomics: a realization's results are
+ * bit-identical whatever the number of realizations, its position among them and its neighbours. The block is read
+ * only. Kernel time is booked under FPTA_K_DENSE, one entry per call.
+ *
+ * fpta_batch_set_os_spectra: after fpta_batch_set_toas (else FPTA_ESTATE); n_comp == 0 clears it, and so does
+ *   fpta_batch_set_toas. Independent of the timing model, the Fourier fit and fpta_batch_set_os. FPTA_EINVAL with the
+ *   reason: everything fpta_batch_set_os refuses, a varied set that is empty, larger than 4, repeats a component or
+ *   does not end in the target, q > 128 ("more than 128"), an unknown or repeated layout signal or one whose mode
+ *   count differs, n_orf outside [0, n_g]. rank_out NULL or [n_psr].
+ * fpta_batch_os_spectra: the statistic of the context's last block (FPTA_ESTATE without a block or without a statistic
+ *   set). The tables are those of fpta_batch_synth_spectra with n_rows[t] = the block's realizations, validated the
+ *   same way before anything is uploaded or launched; a table for a signal outside the varied set is FPTA_EINVAL
+ *   naming the signal. n_tab = 0: the layout's amplitudes for every realization. Each output may be NULL: Q
+ *   [n_g][n_real], Q_mode [n_g][N][n_real], X [n_psr][K][n_real], norm [n_g][n_real], joint [n_orf][n_orf][n_real],
+ *   nab [n_real][n_psr][n_psr] (the entries a >= b; the others are 0), zp [n_real][n_psr][K][K] (Z'). */
+int fpta_batch_set_os_spectra(fpta_ctx* ctx, int32_t n_comp, const int32_t* n_modes, const double* f,
+                              int32_t f_is_common, const double* idx, const double* freqf,
+                              const double* phi /* [n_psr][sum_c N_c] */,
+                              const uint8_t* mask /* NULL or [n_comp][n_toa_total] */, int32_t target,
+                              const double* phi_hat /* [N_target] */, int32_t n_vary, const int32_t* vary,
+                              const int32_t* vary_seg, int32_t n_col, const double* M /* [n_toa_total][n_col] */,
+                              const int32_t* ncol_psr, const double* weights, double rcond, int32_t n_g,
+                              const double* G /* [n_g][n_psr][n_psr] */, int32_t n_orf, int32_t* rank_out);
+int fpta_batch_os_spectra(fpta_ctx* ctx, int32_t n_tab, const int32_t* seg, const int32_t* form,
+                          const int32_t* per_pulsar, const int32_t* n_rows, const double* const* tables, double* Q,
+                          double* Q_mode, double* X, double* norm, double* joint, double* nab, double* zp);
+
 /* Likelihood ratio of a common process on a spectrum grid: per realization of a block the Gaussian log-likelihood as a
  * function of the target's spectrum, against "no such process", on G grid points (added without a change of
  * FPTA_VERSION: no existing call changes). This text is the specification.
