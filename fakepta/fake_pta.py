@@ -556,6 +556,22 @@ def optimal_statistic_array(psrs, target=None, orfs=('hd',), bins=None, template
                                per_mode=per_mode)
 
 
+def optimal_statistic_scrambles_array(psrs, n=1000, seed=0, max_match=0.1, target=None, orfs=('hd',), template=None,
+                                      signals=None, marginalize_tm=True, weights='white', rcond=None, positions=None,
+                                      matrices=None, full=False):
+    """The significance of the optimal statistic of psr.residuals by sky scrambles, for a whole array in ONE GPU call
+    (not in the reference): the statistic under the Hellings-Downs matrices of n fictitious skies whose match with the
+    first ORF is at most max_match (fakepta_amd.os.sky_scrambles; or the given positions [J, P, 3] / matrices
+    [J, P, P]), and the rank of the observed S/N among them. The noise model, target, template and weights are
+    optimal_statistic_array's. Returns a dict: p_value = (1 + count_ge) / (1 + J), snr and count_ge [n_orf, 1],
+    null_mean, null_std and null_max [1], match [J, n_orf], norm [J], positions, and snr_null [J, 1] with full=True
+    (fakepta_amd.os.derive_scrambles). residuals and signal_model are untouched."""
+    from fakepta_amd import os as _os
+    return _os.scrambles_array(psrs, n=n, seed=seed, max_match=max_match, target=target, orfs=orfs, template=template,
+                               signals=signals, Mmats='tm' if marginalize_tm else None, weights=weights, rcond=rcond,
+                               positions=positions, matrices=matrices, full=full)
+
+
 def likelihood_grid_array(psrs, target=None, phi=None, log10_A=None, gamma=None, signals=None, marginalize_tm=True,
                           weights='white', rcond=None, per_pulsar=False, posterior=False):
     """The Gaussian log-likelihood ratio of psr.residuals on a grid of spectra of the target process, for a whole array

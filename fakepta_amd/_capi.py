@@ -62,6 +62,13 @@ _SIGS = [
     ("fpta_batch_os", _c_int, [_ctx_p, _vp, _vp, _vp]),
     ("fpta_os_statistic", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
                                    _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fpta_batch_set_os_scrambles", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _vp]),
+    ("fpta_batch_os_scrambles_info", _c_int, [_ctx_p, _vp]),
+    ("fpta_batch_os_scrambles", _c_int, [_ctx_p, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fpta_os_scrambles", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
+                                    _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fpta_os_scramble_match", _c_int, [_ctx_p, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     ("fpta_batch_set_os_spectra", _c_int, [_ctx_p, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp,
                                            _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _i32, _vp]),
     ("fpta_batch_os_spectra", _c_int, [_ctx_p, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -171,6 +178,7 @@ EPHEM_MSUN = 1.327124400e20 / 6.6743e-11  # FPTA_EPHEM_MSUN
 TM_MAX_COL = 16  # columns of one pulsar's design matrix (fpta_tm_project, fpta_batch_set_timing_model)
 FIT_MAX_COMP, FIT_MAX_COEF = 4, 512  # components and Fourier columns of one fit (fpta_batch_set_fit)
 OS_MAX_COMP, OS_MAX_COL, OS_MAX_COEF = 8, 1024, 512  # components, all Fourier columns, the target's (fpta_batch_set_os)
+SCR_MAX, SCR_MAX_BYTES, SCR_PAIR_PAD = 65536, 8 << 30, 16  # scrambles, bytes of their pair rows (fpta_batch_set_os_scrambles)
 OSS_MAX_VARY, OSS_MAX_COL = 4, 128  # varied components and their Fourier columns (fpta_batch_set_os_spectra)
 LNL_MAX_COEF, LNL_MAX_GRID = 256, 4096  # the target's Fourier columns and the grid points (fpta_batch_set_lnl)
 CLNL_MAX_ORF, CLNL_MAX_N, CLNL_BUDGET = 8, 16384, 32 << 30  # ORFs, n = P K and cached bytes (fpta_batch_set_clnl)
@@ -821,6 +829,107 @@ class Context:
         X = np.empty((self.batch_info()["n_psr"], have["K"], R)) if coefficients else None
         self._check(_lib.fpta_batch_os(self._h, _ptr(Q), _ptr(Qm), _ptr(X)), "fpta_batch_os")
         return Q, Qm, X
+
+    @staticmethod
+    def _scramble_args(what, P, pos, G):
+        """The scrambles of a call as contiguous float64: positions [J, P, 3] or matrices [J, P, P], exactly one of
+        them. Returns (J, pos or None, G or None)."""
+        if (pos is None) == (G is None):
+            raise ValueError(f"{what}: exactly one of positions and matrices must be given")
+        if pos is not None:
+            pos = _f64(pos)
+            if pos.ndim != 3 or pos.shape[1:] != (P, 3):
+                raise ValueError(f"{what}: positions must be [J, {P}, 3], got {pos.shape}")
+            return len(pos), pos, None
+        G = _f64(G)
+        if G.ndim == 2:
+            G = np.ascontiguousarray(G[None])
+        if G.ndim != 3 or G.shape[1:] != (P, P):
+            raise ValueError(f"{what}: matrices must be [J, {P}, {P}], got {G.shape}")
+        return len(G), None, G
+
+    def batch_set_os_scrambles(self, pos=None, G=None):
+        """The sky scrambles of the batch layout's optimal statistic (fpta_batch_set_os_scrambles): fictitious
+        positions pos [J, P, 3] (unit vectors; their Hellings-Downs matrices are made on the device) or explicit
+        symmetric matrices G [J, P, P]. Neither, or an empty one, clears them. Returns (norm [J], match [J, n_g])
+        against the n_g matrices of the statistic that is set."""
+        have = self.batch_os_info()
+        n_g = have["J"]
+        if have["K"] == 0:  # no statistic: the library's own state error
+            self._check(_lib.fpta_batch_set_os_scrambles(self._h, 1, None, None, None, None),
+                        "fpta_batch_set_os_scrambles")
+        if (pos is None and G is None) or len(pos if pos is not None else G) == 0:
+            self._check(_lib.fpta_batch_set_os_scrambles(self._h, 0, None, None, None, None),
+                        "fpta_batch_set_os_scrambles")
+            return np.zeros(0), np.zeros((0, n_g))
+        J, pos, G = self._scramble_args("batch_set_os_scrambles", self.batch_info()["n_psr"], pos, G)
+        norm, match = np.zeros(J), np.zeros((J, n_g))
+        self._check(_lib.fpta_batch_set_os_scrambles(self._h, J, _ptr(pos), _ptr(G), _ptr(norm), _ptr(match)),
+                    "fpta_batch_set_os_scrambles")
+        return norm, match
+
+    def batch_os_scrambles_info(self):
+        """The scrambles that are set (0: none), the matrices of their statistic, the pairs of a row and the
+        realizations of the last result (fpta_batch_os_scrambles_info)."""
+        return dict(zip(("n_scr", "n_g", "n_pair", "n_real"),
+                        self._info4(_lib.fpta_batch_os_scrambles_info, "fpta_batch_os_scrambles_info")))
+
+    def batch_os_scrambles(self, full=False):
+        """The scrambled statistic of the last block (fpta_batch_os_scrambles): a dict of snr_obs [n_g, R], count_ge
+        [n_g, R] int64, mean, std and max [R] of the null and, with full=True, snr_null [J, R]. The buffers are sized
+        from the library's own counts."""
+        have, R = self.batch_os_scrambles_info(), self._block_real()
+        out = dict(snr_obs=np.zeros((have["n_g"], R)), count_ge=np.zeros((have["n_g"], R), dtype=np.int64),
+                   mean=np.zeros(R), std=np.zeros(R), max=np.zeros(R),
+                   snr_null=np.zeros((have["n_scr"], R)) if full else None)
+        self._check(_lib.fpta_batch_os_scrambles(self._h, _ptr(out["snr_obs"]), _ptr(out["count_ge"]),
+                                                 _ptr(out["mean"]), _ptr(out["std"]), _ptr(out["max"]),
+                                                 _ptr(out["snr_null"])), "fpta_batch_os_scrambles")
+        return out
+
+    def os_scrambles(self, offs, toas, nu, n_modes, f, idx, freqf, phi, target, phi_hat, G, res, pos=None,
+                     matrices=None, masks=None, M=None, ncol_psr=None, weights=None, rcond=None, full=False):
+        """The scrambled optimal statistic of every row of res [n_vec, n_toa] or [n_toa] for any array
+        (fpta_os_scrambles): os_statistic's arguments and the scrambles as batch_set_os_scrambles takes them. A dict:
+        batch_os_scrambles' entries (with full=True also Qs [J, n_vec], the numerators of snr_null), Q [n_g, n_vec],
+        X [P, K, n_vec], norm [J], match [J, n_g] and N_ab [P, P]."""
+        offs, toas, nu, res, P, n, n_vec = self._oneshot_args("os_scrambles", offs, toas, nu, res)
+        n_modes, f, idx, freqf, common, phi, mask, target, phi_hat, G = self._os_args(
+            "os_scrambles", P, n, n_modes, f, idx, freqf, phi, masks, target, phi_hat, G)
+        M, ncol_psr, weights, rcond = self._tm_args("os_scrambles", P, n, M, ncol_psr, weights, rcond)
+        J, pos, matrices = self._scramble_args("os_scrambles", P, pos, matrices)
+        N, n_g = int(n_modes[target]), len(G)
+        out = dict(snr_obs=np.zeros((n_g, n_vec)), count_ge=np.zeros((n_g, n_vec), dtype=np.int64),
+                   mean=np.zeros(n_vec), std=np.zeros(n_vec), max=np.zeros(n_vec),
+                   snr_null=np.zeros((J, n_vec)) if full else None, Qs=np.zeros((J, n_vec)) if full else None,
+                   Q=np.zeros((n_g, n_vec)),
+                   X=np.zeros((P, 2 * N, n_vec)), norm=np.zeros(J), match=np.zeros((J, n_g)), N_ab=np.zeros((P, P)))
+        self._check(_lib.fpta_os_scrambles(
+            self._h, P, _ptr(offs), _ptr(toas), _ptr(nu), len(n_modes), _ptr(n_modes), _ptr(f), int(common), _ptr(idx),
+            _ptr(freqf), _ptr(phi), _ptr(mask), target, _ptr(phi_hat), M.shape[1], _ptr(M), _ptr(ncol_psr),
+            _ptr(weights), rcond, n_g, _ptr(G), J, _ptr(pos), _ptr(matrices), n_vec, _ptr(res), _ptr(out["Q"]),
+            _ptr(out["X"]), _ptr(out["norm"]), _ptr(out["match"]), _ptr(out["snr_obs"]), _ptr(out["count_ge"]),
+            _ptr(out["mean"]), _ptr(out["std"]), _ptr(out["max"]), _ptr(out["snr_null"]), _ptr(out["Qs"]),
+            _ptr(out["N_ab"])),
+            "fpta_os_scrambles")
+        return out
+
+    def os_scramble_match(self, pos, ref, rows=False):
+        """match [J, n_ref] of the Hellings-Downs matrices of the positions pos [J, P, 3] against the reference
+        matrices ref [n_ref, P, P] or [P, P] (fpta_os_scramble_match): sum G_ref G / sqrt(sum G_ref^2 sum G^2) over
+        the pairs. rows=True: (match, the device's pair rows [J, P (P - 1) / 2] in np.tril_indices(P, -1) order)."""
+        ref = _f64(ref)
+        if ref.ndim == 2:
+            ref = np.ascontiguousarray(ref[None])
+        if ref.ndim != 3 or ref.shape[1] != ref.shape[2]:
+            raise ValueError(f"os_scramble_match: the reference must be [n_ref, P, P], got {ref.shape}")
+        J, pos, _ = self._scramble_args("os_scramble_match", ref.shape[1], pos, None)
+        P = ref.shape[1]
+        match = np.zeros((J, len(ref)))
+        out = np.zeros((J, P * (P - 1) // 2)) if rows else None
+        self._check(_lib.fpta_os_scramble_match(self._h, P, J, _ptr(pos), len(ref), _ptr(ref), _ptr(match), _ptr(out)),
+                    "fpta_os_scramble_match")
+        return (match, out) if rows else match
 
     def batch_set_os_spectra(self, n_modes, f, idx, freqf, phi, target, phi_hat, vary, vary_seg, G, n_orf, masks=None,
                              M=None, ncol_psr=None, weights=None, rcond=None):

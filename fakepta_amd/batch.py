@@ -74,6 +74,7 @@ class BatchSimulator:
         self._has_tm = False  # set_timing_model
         self._fit = None  # set_fourier_fit: dict(n_modes, f, idx, freqf, common)
         self._os = None  # set_optimal_statistic: dict(G, nab, n_orf, centres, counts, target, template)
+        self._scr = None  # set_sky_scrambles: dict(J, positions)
         self._oss = None  # set_optimal_statistic_spectra: dict(G, n_orf, centres, counts, target, template, seg, names, K)
         self._lnl = None  # set_likelihood_grid: dict(phi, axes, ld, target)
         self._fe = None  # set_fe_statistic: dict(fgw, sky, n_eff)
@@ -362,6 +363,7 @@ class BatchSimulator:
         M, ncol = _os.design_of(self.psrs, Mmats, "set_optimal_statistic")
         w = _tm.weights_of(self.psrs, weights, self.n_toa)
         self._os = None
+        self._scr = None  # the library clears the scrambles with the statistic they belong to
         rank, nab = self.ctx.batch_set_os(model["n_modes"], model["f"], model["idx"], model["freqf"], model["phi"], t,
                                           phi_hat, G, masks=model["masks"], M=M, ncol_psr=ncol, weights=w, rcond=rcond)
         self._os = dict(G=G, nab=nab, n_orf=n_orf, centres=centres, counts=counts, target=t, template=phi_hat)
@@ -379,6 +381,43 @@ class BatchSimulator:
         o = self._os
         Q, Qm, _ = self.ctx.batch_os(per_mode=per_mode)
         return _os.derive(Q, o["G"], o["nab"], o["n_orf"], o["centres"], o["counts"], Qm)
+
+    def set_sky_scrambles(self, n=1000, seed=0, max_match=0.1, positions=None, matrices=None):
+        """Set the sky scrambles that sky_scrambles() ranks the optimal statistic against (after
+        set_optimal_statistic, which also clears them; fpta_batch_set_os_scrambles). By default n fictitious skies from
+        fakepta_amd.os.sky_scrambles(seed=seed) whose Hellings-Downs matrices have |match| <= max_match with the first
+        ORF of the statistic; or positions [J, P, 3] (unit vectors), or explicit symmetric matrices [J, P, P] (any
+        other ORF scrambled by the caller). n = 0 clears them. Returns (match [J, n_orf], norm [J]): the match with
+        every ORF of the statistic and the denominators sum_{a<b} G_j^2 N_ab."""
+        o = getattr(self, "_os", None)
+        if o is None:
+            raise ValueError("set_sky_scrambles: no optimal statistic is set; call set_optimal_statistic() first")
+        if positions is not None and matrices is not None:
+            raise ValueError("set_sky_scrambles: give positions or matrices, not both")
+        if positions is None and matrices is None:
+            if int(n) == 0:
+                self.ctx.batch_set_os_scrambles()
+                self._scr = None
+                return np.zeros((0, o["n_orf"])), np.zeros(0)
+            positions, _ = _os.sky_scrambles(self.ctx, self.psrs, n, seed=seed, max_match=max_match, ref=o["G"][:1])
+        # a refused call leaves the library's scrambles, and this record of them, as they were
+        norm, match = self.ctx.batch_set_os_scrambles(pos=positions, G=matrices)
+        self._scr = dict(J=len(norm), positions=None if positions is None else np.asarray(positions, dtype=np.float64))
+        return match[:, :o["n_orf"]], norm
+
+    def sky_scrambles(self, full=False):
+        """The sky-scramble significance of the optimal statistic of every realization of the last block, computed on
+        the device; the block is untouched. A dict: p_value = (1 + count_ge) / (1 + J), snr and count_ge [n_orf, R]
+        (the observed S/N of each ORF and the scrambles at or above it), null_mean, null_std and null_max [R] of the
+        scrambled S/N, and snr_null [J, R] with full=True. Per batch of a sharded job: simulate_sharded(...,
+        on_batch=lambda sim, first, n: ...sim.sky_scrambles()["p_value"]...)."""
+        o = getattr(self, "_os", None)
+        if o is None:
+            raise ValueError("sky_scrambles: no optimal statistic is set; call set_optimal_statistic() first")
+        got = self.ctx.batch_os_scrambles(full=full)
+        J = self.ctx.batch_os_scrambles_info()["n_scr"]
+        return _os.derive_scrambles(got["snr_obs"], got["count_ge"], J, got["mean"], got["std"], got["max"],
+                                    o["n_orf"], got["snr_null"])
 
     def set_optimal_statistic_spectra(self, vary, target=None, orfs=("hd",), bins=None, template=None, noise="layout",
                                       Mmats="tm", weights="white", rcond=None):

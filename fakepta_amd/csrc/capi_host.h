@@ -19,6 +19,10 @@
 
 using namespace fpta;
 
+namespace fpta_os {
+struct Plan;  // os_host.h
+}
+
 namespace __attribute__((visibility("hidden"))) capi {  // library-internal: not exported
 
 extern thread_local std::string g_err;  // the last error of a call without a context
@@ -207,10 +211,13 @@ struct FitState {
 };
 
 // Optimal statistic: k_fit_apply's second operator slot (B_p, X), the template phi_hat [N], the J pair-weight matrices
-// [J][P][P] and the results Q_mode [J][N][rpad], Q [J][rpad]
+// [J][P][P] and the results Q_mode [J][N][rpad], Q [J][rpad]; the plan's N_ab [P][P] for the sky scrambles, on the
+// device and on the host
+constexpr int kOsRpad = 32;  // k_fit_apply's realization padding, which the statistic's kernels rely on
 struct OsSlot {
   FitSlot x;
-  DevBuf phi, g, qm, q;
+  DevBuf phi, g, qm, q, nab;
+  std::vector<double> h_nab;
 };
 struct OsState {
   bool set = false;
@@ -276,6 +283,21 @@ struct OssState {
   void clear() { *this = OssState(); }
 };
 
+// Sky scrambles of the optimal statistic (os_scramble.hip), on top of an OsSlot: the pair map [n_pair_pad][2], the
+// scrambles' pair rows Gs [J][n_pair_pad] with norm [J] and match [J][n_orf], the observed ORFs' rows Go
+// [n_orf][n_pair_pad] with their norms and sums of squares, the call's inputs (positions or matrices), and the results
+// Y [n_pair_pad][rpad], Qs [J][rpad], snr_obs and count_ge [n_orf][rpad], the null's mean, std and max [3][rpad] and,
+// when asked for, snr_null [J][rpad]
+struct ScrSlot {
+  DevBuf map, in, gs, norm, ss, match, go, onorm, oss, y, qs, snr, cnt, mom, null;
+};
+struct ScrState {
+  bool set = false;
+  int32_t J = 0, n_orf = 0, R = 0, rpad = 0;  // J scrambles against the n_orf matrices of the statistic that is set
+  int64_t n_pair = 0, n_pad = 0;
+  void clear() { *this = ScrState(); }
+};
+
 }  // namespace capi
 
 using namespace capi;
@@ -325,6 +347,8 @@ struct fpta_ctx {
   DevBuf cross_rows, cross_x;
   OsSlot os, os1;
   OsState os_st;
+  ScrSlot scr, scr1;
+  ScrState scr_st;
   LnlSlot lnl, lnl1;
   LnlState lnl_st;
   FeSlot fe, fe1;
@@ -339,6 +363,7 @@ struct fpta_ctx {
     tm_st.clear();
     fit_st.clear();
     os_st.clear();
+    scr_st.clear();
     lnl_st.clear();
     fe_st.clear();
     clnl_st.clear();
@@ -637,6 +662,13 @@ int fit_download(fpta_ctx* c, const DevBuf& coef, int64_t rows, int32_t R, int32
 // [N] and J >= 1 matrices G: Q_mode into qm [J][N][R_pad], Q into q [J][R_pad]. No timer entry: the caller's spans it.
 int os_pairs_launch(fpta_ctx* c, const double* X, const double* phi, const double* G, double* qm, double* q,
                     int32_t n_psr, int32_t N, int32_t R_pad, int32_t J);
+
+// os.hip, for os_scramble.hip: the upload of a plan's tables into a slot, both stages on a block without a timer entry
+// (the caller's spans them; st.rpad is set), and the download of the wanted results
+int os_upload(fpta_ctx* c, const fpta_os::Plan& plan, int32_t n_psr, const int64_t* offs, const double* phi_hat,
+              int32_t n_g, const double* G, OsSlot& s);
+int os_launch_unbooked(fpta_ctx* c, const Block& b, OsSlot& s, OsState& st);
+int os_results(fpta_ctx* c, const Block& b, const OsSlot& s, const OsState& st, double* Q, double* Q_mode, double* X);
 
 // cw_batch.hip: the one-table mode of an injection, every realization of the block getting the same delay vector.
 // bcast_vector sizes v [n_toa of the batch layout] and clears it; the caller's drop-in kernel fills it; bcast_add

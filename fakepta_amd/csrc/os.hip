@@ -27,7 +27,7 @@ constexpr int kOsReal = 16;   // realizations of a workgroup
 constexpr int kOsWaves = 4;   // waves of a workgroup
 constexpr int kOsRW = kOsReal / kOsWaves;  // realizations of a wave
 constexpr int kOsJ = 8;       // pair-weight matrices of a workgroup, at most
-constexpr int kOsRpad = 32;   // k_fit_apply's realization padding: a multiple of kOsReal
+// (kOsRpad, k_fit_apply's realization padding, a multiple of kOsReal: capi_host.h)
 static_assert(kOsRpad % kOsReal == 0 && kOsReal == 16 && kOsWaves * 64 == 256,
               "k_os_pairs stages 16 x 16 tiles with 256 threads and never reads past the padded realizations");
 
@@ -141,14 +141,16 @@ __global__ __launch_bounds__(256) void k_os_reduce(const double* __restrict__ Qm
   Q[e] = s;
 }
 
-// Device copies of a plan's tables, the template and the matrices
-static int os_upload(fpta_ctx* c, const fpta_os::Plan& plan, int32_t n_psr, const int64_t* offs, const double* phi_hat,
+// Device copies of a plan's tables, the template and the matrices, and N_ab (the sky scrambles' denominators)
+int os_upload(fpta_ctx* c, const fpta_os::Plan& plan, int32_t n_psr, const int64_t* offs, const double* phi_hat,
                      int32_t n_g, const double* G, OsSlot& s) {
   int rc;
   if ((rc = fit_upload(c, "os", s.x, plan.K, plan.B, n_psr, offs, plan.rows))) return rc;
   if ((rc = upload(c, s.phi, phi_hat, sizeof(double) * (size_t)plan.N, "os template"))) return rc;
   if ((rc = upload(c, s.g, G, sizeof(double) * (size_t)n_g * (size_t)n_psr * (size_t)n_psr, "os pair weights")))
     return rc;
+  s.h_nab = plan.Nab;
+  if ((rc = upload(c, s.nab, plan.Nab.data(), sizeof(double) * plan.Nab.size(), "os pair norms"))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream), "os upload sync");
   return FPTA_OK;
 }
@@ -156,15 +158,22 @@ static int os_upload(fpta_ctx* c, const fpta_os::Plan& plan, int32_t n_psr, cons
 // Both stages on a block of st.K columns and st.J matrices; one FPTA_K_DENSE entry. The results stay in the slot, padded
 // to st.rpad realizations: X [P][K][rpad], Q_mode [J][N][rpad], Q [J][rpad].
 static int os_launch(fpta_ctx* c, const Block& b, OsSlot& s, OsState& st) {
+  if ((st.J + kOsJ - 1) / kOsJ > 65535 || st.K / 2 > 65535)  // refused before the timer entry opens
+    return fail(c, FPTA_EINVAL, "os: too many pair-weight matrices or modes");
+  KTimer kt(c, FPTA_K_DENSE);
+  return os_launch_unbooked(c, b, s, st);
+}
+
+// The same without the timer entry (os_scramble.hip's spans its own kernels too)
+int os_launch_unbooked(fpta_ctx* c, const Block& b, OsSlot& s, OsState& st) {
   const int32_t R = b.R, n_psr = b.n_psr, K = st.K, J = st.J, N = K / 2;
   const int32_t R_pad = st.rpad = (R + kOsRpad - 1) / kOsRpad * kOsRpad;
   const size_t b_x = sizeof(double) * (size_t)n_psr * (size_t)K * (size_t)R_pad;
   const size_t b_qm = sizeof(double) * (size_t)J * (size_t)N * (size_t)R_pad, b_q = sizeof(double) * (size_t)J * R_pad;
   if (s.x.coef.ensure(b_x) != hipSuccess || s.qm.ensure(b_qm) != hipSuccess || s.q.ensure(b_q) != hipSuccess)
     return fail(c, FPTA_ENOMEM, "os: no device memory for " + std::to_string(b_x + b_qm + b_q) + " bytes of results");
-  if ((J + kOsJ - 1) / kOsJ > 65535 || N > 65535)  // refused before the timer entry opens
+  if ((J + kOsJ - 1) / kOsJ > 65535 || N > 65535)
     return fail(c, FPTA_EINVAL, "os: too many pair-weight matrices or modes");
-  KTimer kt(c, FPTA_K_DENSE);
   int32_t rp = 0;
   int rc = fit_launch_unbooked(c, b, K, s.x, rp);
   if (rc) return rc;
@@ -209,7 +218,7 @@ int os_pairs_launch(fpta_ctx* c, const double* X, const double* phi, const doubl
 }
 
 // The wanted results of os_launch on that block, unpadded
-static int os_results(fpta_ctx* c, const Block& b, const OsSlot& s, const OsState& st, double* Q, double* Q_mode,
+int os_results(fpta_ctx* c, const Block& b, const OsSlot& s, const OsState& st, double* Q, double* Q_mode,
                       double* X) {
   int rc;
   if (Q && st.J > 0 && (rc = fit_download(c, s.q, st.J, b.R, st.rpad, Q))) return rc;
@@ -232,6 +241,7 @@ extern "C" int fpta_batch_set_os(fpta_ctx* c, int32_t n_comp, const int32_t* n_m
   if (L.P <= 0) return fail(c, FPTA_ESTATE, "set_os: set_toas first");
   if (n_comp == 0) {
     c->os_st.clear();
+    c->scr_st.clear();
     if (rank_out) std::fill(rank_out, rank_out + L.P, 0);
     return FPTA_OK;
   }
@@ -245,6 +255,7 @@ extern "C" int fpta_batch_set_os(fpta_ctx* c, int32_t n_comp, const int32_t* n_m
   if (made) return fail(c, made == 2 ? FPTA_ENOMEM : FPTA_EINVAL, "set_os: " + why);
   HIPCHK(c, hipSetDevice(c->device), "hipSetDevice");
   c->os_st.clear();
+  c->scr_st.clear();  // the scrambles' norms and matches were this statistic's
   // a statistic with the previous operator may still read the tables
   HIPCHK(c, hipStreamSynchronize(c->stream), "set_os sync");
   int rc;

@@ -159,6 +159,128 @@ def derive_per_realization(Q, norm, joint, n_orf, centres=None, counts=None, Q_m
     return out
 
 
+# ----------------------------------------------------------------------------- sky scrambles
+def scramble_positions(n, P, seed=0):
+    """n sets of P directions, uniform on the sphere: unit vectors [n, P, 3] from np.random.default_rng(seed). Drawn on
+    the host, like the continuous-wave populations: the seed fixes them whatever the device."""
+    n, P = int(n), int(P)
+    if n < 0 or P < 1:
+        raise ValueError(f"scramble_positions: n must be >= 0 and P >= 1, got {n} and {P}")
+    rng = np.random.default_rng(seed)
+    z = rng.uniform(-1.0, 1.0, (n, P))
+    lon = rng.uniform(0.0, 2.0 * np.pi, (n, P))
+    s = np.sqrt(1.0 - z * z)
+    pos = np.stack([s * np.cos(lon), s * np.sin(lon), z], axis=-1)
+    return np.ascontiguousarray(pos / np.linalg.norm(pos, axis=-1, keepdims=True))
+
+
+def _positions_of(psrs_or_pos):
+    """[P, 3] float64 from an array of positions or from pulsars with a pos attribute."""
+    if isinstance(psrs_or_pos, np.ndarray) or not hasattr(psrs_or_pos[0], "pos"):
+        pos = np.asarray(psrs_or_pos, dtype=np.float64)
+    else:
+        pos = np.array([np.asarray(p.pos, dtype=np.float64) for p in psrs_or_pos])
+    if pos.ndim != 2 or pos.shape[1] != 3 or len(pos) < 2:
+        raise ValueError(f"sky_scrambles: the true positions must be [P >= 2, 3], got {pos.shape}")
+    return pos
+
+
+def hd_matrix(pos):
+    """Hellings-Downs [P, P] of unit positions [P, 3], fakepta.correlated_noises.hd's formula, zero diagonal."""
+    pos = np.asarray(pos, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x = (1 - pos @ pos.T) / 2
+        g = 1.5 * x * np.log(x) - 0.25 * x + 0.5
+    np.fill_diagonal(g, 0.0)
+    return g
+
+
+def sky_scrambles(ctx, psrs_or_pos, n, seed=0, max_match=0.1, ref="hd", max_tries=20):
+    """n sky scrambles of a small match with the true sky: candidates from scramble_positions (batches of max(2 n,
+    256), batch b seeded [seed, b]), their match with the reference computed on the device (fpta_os_scramble_match),
+    the first n with |match| <= max_match kept in the order drawn. ref: "hd", the Hellings-Downs matrix of the true
+    positions, or explicit matrices [n_ref, P, P] (every one of them has to be matched that little). Returns
+    (positions [n, P, 3], match [n, n_ref]). ValueError with the acceptance rate when max_tries batches do not give
+    n."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"sky_scrambles: n must be >= 0, got {n}")
+    if isinstance(ref, str):
+        if ref != "hd":
+            raise ValueError(f"sky_scrambles: ref must be 'hd' or explicit matrices, got {ref!r}")
+        ref_m = hd_matrix(_positions_of(psrs_or_pos))[None]
+    else:
+        ref_m = np.asarray(ref, dtype=np.float64)
+        ref_m = ref_m[None] if ref_m.ndim == 2 else ref_m
+    P = ref_m.shape[-1]
+    kept, matches, have, drawn = [], [], 0, 0
+    batch = max(2 * n, 256)
+    for b in range(int(max_tries)):
+        if have >= n:
+            break
+        cand = scramble_positions(batch, P, [int(seed), b])
+        m = ctx.os_scramble_match(cand, ref_m)
+        ok = np.all(np.abs(m) <= max_match, axis=1)
+        kept.append(cand[ok])
+        matches.append(m[ok])
+        have += int(ok.sum())
+        drawn += batch
+    if have < n:
+        raise ValueError(f"sky_scrambles: {have} of {drawn} candidates have |match| <= {max_match} (acceptance rate "
+                         f"{have / max(drawn, 1):.3g}), fewer than the {n} asked for; raise max_match or max_tries")
+    pos = np.concatenate(kept)[:n] if kept else np.zeros((0, P, 3))
+    return np.ascontiguousarray(pos), np.concatenate(matches)[:n] if matches else np.zeros((0, len(ref_m)))
+
+
+def derive_scrambles(snr_obs, count_ge, n_scr, mean=None, std=None, mx=None, n_orf=None, snr_null=None):
+    """What the host derives from the device's ranks: p_value = (1 + count_ge) / (1 + J) (the observed sky counts as
+    one of its own scrambles, so no p-value is 0), snr and count_ge [n_orf, R] (the first n_orf rows; None: all), and
+    the null's moments null_mean, null_std, null_max [R] and snr_null [J, R] passed through when given."""
+    snr_obs = np.asarray(snr_obs, dtype=np.float64)
+    count_ge = np.asarray(count_ge)
+    if not np.issubdtype(count_ge.dtype, np.integer):
+        raise ValueError("derive_scrambles: count_ge must be integer counts")
+    n_scr = int(n_scr)
+    if n_scr < 1 or np.any(count_ge < 0) or np.any(count_ge > n_scr):
+        raise ValueError(f"derive_scrambles: counts outside [0, {n_scr}]")
+    k = len(snr_obs) if n_orf is None else int(n_orf)
+    out = dict(p_value=(1.0 + count_ge[:k]) / (1.0 + n_scr), snr=snr_obs[:k], count_ge=count_ge[:k])
+    for key, v in (("null_mean", mean), ("null_std", std), ("null_max", mx), ("snr_null", snr_null)):
+        if v is not None:
+            out[key] = v
+    return out
+
+
+def scrambles_array(psrs, n=1000, seed=0, max_match=0.1, target=None, orfs=("hd",), template=None, signals=None,
+                    Mmats="tm", weights="white", rcond=None, positions=None, matrices=None, full=False, ctx=None):
+    """The sky-scramble null distribution of the optimal statistic of psr.residuals for a whole array in one device
+    call (fpta_os_scrambles): derive_scrambles' dict for one residual vector (R = 1) plus match [J, n_orf], norm [J]
+    and positions (when they were drawn here or given). The noise model is statistic_array's. The scrambles are
+    sky_scrambles(ctx, psrs, n, seed, max_match) against the first ORF, or the given positions / matrices."""
+    segs = segments_of(psrs, signals)
+    t = pick_target(segs, target)
+    model = noise_model(segs, len(psrs))
+    phi_hat = template_of(model, t, template)
+    G, n_orf, _, _ = pair_matrices(psrs, orfs, None)
+    M, ncol = design_of(psrs, Mmats, "optimal_statistic_scrambles_array")
+    offs = np.concatenate([[0], np.cumsum([len(p.toas) for p in psrs])]).astype(np.int64)
+    toas = np.concatenate([np.asarray(p.toas, dtype=np.float64) for p in psrs])
+    nu = np.concatenate([np.asarray(p.freqs, dtype=np.float64) for p in psrs])
+    res = np.concatenate([np.asarray(p.residuals, dtype=np.float64) for p in psrs])
+    ctx = ctx if ctx is not None else _capi.get_context()
+    if positions is None and matrices is None:
+        positions, _ = sky_scrambles(ctx, psrs, n, seed=seed, max_match=max_match, ref=G[:1])
+    got = ctx.os_scrambles(offs, toas, nu, model["n_modes"], model["f"], model["idx"], model["freqf"], model["phi"], t,
+                           phi_hat, G, res, pos=positions, matrices=matrices, masks=model["masks"], M=M, ncol_psr=ncol,
+                           weights=_tm.weights_of(psrs, weights, int(offs[-1])), rcond=rcond, full=full)
+    out = derive_scrambles(got["snr_obs"], got["count_ge"], len(got["norm"]), got["mean"], got["std"], got["max"],
+                           n_orf, got["snr_null"])
+    out.update(match=got["match"][:, :n_orf], norm=got["norm"], Q=got["Q"])
+    if positions is not None:
+        out["positions"] = np.asarray(positions, dtype=np.float64)
+    return out
+
+
 def noise_model(segments, n_psr):
     """BatchSimulator-style segments (dicts with name, kind 0 per-pulsar f, amp [P, N] / 1 common f, amp [N], idx,
     freqf, mask) -> dict(names, n_modes [C] int32, f [sum N] or [P, sum N], idx, freqf, phi [P, sum N] = amp^2, masks).

@@ -423,6 +423,67 @@ int fpta_os_statistic(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const d
                       const double* res /* [n_vec][n_toa_total] */, double* Q, double* Q_mode, double* X,
                       int32_t* rank_out, double* nab_out);
 
+/* ---- sky scrambles of the optimal statistic ----
+ * The significance of an optimal-statistic S/N by sky scrambles (Cornish & Sampson 2016; Taylor et al. 2017): the
+ * statistic above under n_scr further pair-weight matrices, and the rank of the observed S/N among them (added without
+ * a change of FPTA_VERSION: no existing call changes). This text is the specification.
+ * A scramble j is a set of fictitious unit position vectors pos[j] [n_psr][3], whose matrix is Hellings-Downs,
+ *   x = (1 - p_a . p_b) / 2 (every operation rounded once, the two leading products summed first),
+ *   G_ab = 1.5 x ln x - x / 4 + 1 / 2,
+ * or an explicit symmetric matrix G[j] [n_psr][n_psr]. Only the pairs a > b enter; they are kept as rows
+ * Gs [n_scr][n_pair_pad] in the order of numpy's tril_indices(n_psr, -1), pair e = a (a - 1) / 2 + b, n_pair_pad the
+ * next multiple of 16 (zero padding). With X_p, phi_hat and N_ab of the statistic that is set, per realization r:
+ *   Y_ab[r] = sum_k phi_hat_k X_a,k X_b,k  over the K = 2 N columns (cosines, then sines), made once per block,
+ *   Qs[j][r] = sum_{a>b} Gs[j][ab] Y_ab[r]   (one fp64 MFMA product [n_scr, n_pair] x [n_pair, n_real]),
+ *   norm[j] = sum_{a>b} Gs[j][ab]^2 N_ab,   snr_null[j][r] = Qs[j][r] / sqrt(norm[j]),
+ *   snr_obs[o][r] = Q[o][r] / sqrt(sum_{a>b} G_o[ab]^2 N_ab) for each of the n_g matrices G_o of the statistic,
+ *   count_ge[o][r] = #{j : snr_null[j][r] >= snr_obs[o][r]},
+ *   mean, std (ddof = 0, two passes in scramble order) and max of snr_null[.][r],
+ *   match[j][o] = sum Gs[j] G_o / sqrt(sum G_o^2 sum Gs[j]^2), unweighted sums over the pairs a > b.
+ * snr_obs and snr_null come from one device function. Fixed operation order, no atomics: a scramble's row of Qs is
+ * bit-identical whatever the other scrambles, a realization's column whatever the number of realizations, its
+ * position among them and its neighbours. The block is read only. An observed matrix without a pair of positive N_ab
+ * has snr_obs NaN or infinite and count_ge 0.
+ * Validated on the host before anything is uploaded or launched (FPTA_EINVAL with the reason; a refused call leaves
+ * the previous set in place): n_scr > 65536, pair rows of more than 8 GiB (8 n_scr n_pair_pad bytes), not exactly one
+ * of pos and G, n_psr < 2, a position that is not finite or not of unit length within 1e-12, a matrix that is not
+ * symmetric, a pair weight that is not finite (coincident directions; the message names scramble and pair), a scramble
+ * whose norm is not positive.
+ *
+ * fpta_batch_set_os_scrambles: the scrambles of the batch layout's statistic (after fpta_batch_set_os, else
+ *   FPTA_ESTATE). n_scr == 0 clears them, and so do fpta_batch_set_os and fpta_batch_set_toas. norm_out NULL or
+ *   [n_scr], match_out NULL or [n_scr][n_g].
+ * fpta_batch_os_scrambles_info: info[0] = n_scr of the set (0: none), info[1] = n_g, info[2] = n_pair, info[3] = the
+ *   realizations of the last fpta_batch_os_scrambles result (0: none).
+ * fpta_batch_os_scrambles: on the context's last block and stream (FPTA_ESTATE without a block, a statistic or
+ *   scrambles). It runs both stages of fpta_batch_os first, whose results are then those of fpta_batch_os alone, then
+ *   k_scr_pairs, k_scr_gemm and k_scr_rank; one FPTA_K_DENSE entry. Each output may be NULL: snr_obs and count_ge
+ *   [n_g][n_real], mean, std and max [n_real], snr_null [n_scr][n_real] (kept on the device only when asked for).
+ * fpta_os_scrambles: one call for any array and n_vec residual vectors, fpta_os_statistic's arguments and the scramble
+ *   inputs; the same kernels. Q NULL or [n_g][n_vec], X NULL or [n_psr][K][n_vec], qs NULL or [n_scr][n_vec] (Qs
+ *   itself), nab_out NULL or [n_psr][n_psr].
+ * fpta_os_scramble_match: match [n_scr][n_ref] of the Hellings-Downs matrices of pos [n_scr][n_psr][3] against any
+ *   reference matrices ref [n_ref][n_psr][n_psr], without a statistic (drawing scrambles of a small match);
+ *   rows_out gets the device's pair rows, unpadded. */
+int fpta_batch_set_os_scrambles(fpta_ctx* ctx, int32_t n_scr, const double* pos /* NULL or [n_scr][n_psr][3] */,
+                                const double* G /* NULL or [n_scr][n_psr][n_psr] */, double* norm_out,
+                                double* match_out);
+int fpta_batch_os_scrambles_info(fpta_ctx* ctx, int64_t* info /* [4] */);
+int fpta_batch_os_scrambles(fpta_ctx* ctx, double* snr_obs, int64_t* count_ge, double* mean, double* std_out,
+                            double* max_out, double* snr_null);
+int fpta_os_scrambles(fpta_ctx* ctx, int32_t n_psr, const int64_t* offs, const double* toas, const double* nu,
+                      int32_t n_comp, const int32_t* n_modes, const double* f, int32_t f_is_common,
+                      const double* idx, const double* freqf, const double* phi, const uint8_t* mask, int32_t target,
+                      const double* phi_hat, int32_t n_col, const double* M, const int32_t* ncol_psr,
+                      const double* weights, double rcond, int32_t n_g, const double* G, int32_t n_scr,
+                      const double* scr_pos, const double* scr_G, int32_t n_vec,
+                      const double* res /* [n_vec][n_toa_total] */, double* Q, double* X, double* norm_out,
+                      double* match_out, double* snr_obs, int64_t* count_ge, double* mean, double* std_out,
+                      double* max_out, double* snr_null, double* qs, double* nab_out);
+int fpta_os_scramble_match(fpta_ctx* ctx, int32_t n_psr, int32_t n_scr, const double* pos, int32_t n_ref,
+                           const double* ref /* [n_ref][n_psr][n_psr] */, double* match_out,
+                           double* rows_out /* NULL or [n_scr][n_pair] */);
+
 /* ---- optimal statistic under a noise spectrum per realization ----
  * The statistic above with P_p of realization r built from row r of per-realization spectra, the tables of
  * fpta_batch_synth_spectra: every realization of a block is weighted by its own noise model (a P-P run, a population
